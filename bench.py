@@ -10,6 +10,10 @@ step uses a different angle; the roofline object is quoted on the same launches.
 N > 1 (torchrun, one rank per GPU): the global volume is (N*512) x 512 x 512, slab-partitioned along axis 0;
 halos are exchanged once at upload over RCCL, steps need no communication (weak scaling).
 
+A plain run sets up, warms up, times the steps and prints the headline line; `--full` adds what takes runs of its own or is
+not the headline: the per-angle distribution, the measured traffic of the committed profiles, the `extra` configurations and
+the CPU baseline.  `--dump-outputs DIR` writes the output of the last timed step (dump_outputs()).
+
 Output: ONE JSON line on rank 0.
 """
 import argparse
@@ -39,7 +43,37 @@ def parse():
     ap.add_argument('--no-extra-1024', action='store_true', help='skip the 1024^3 trilinear entry of `extra`')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='target wall time of the CPU baseline sample')
+    ap.add_argument('--full', action='store_true', help='also the per-angle distribution, the measured traffic, the `extra` '
+                    'configurations and the CPU baseline (a plain run measures the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the output of the last timed step to DIR as .npy (float32; '
+                    'a fixed, seeded sample of it when large)')
     return ap.parse_args()
+
+
+DUMP_VOXELS = 1 << 22          # 16 MB of float32 over all ranks
+
+
+def dump_outputs(out, directory, rank, world):
+    """The output buffer of the last timed step, as the caller of `affine(..., output=out)` holds it.  Up to DUMP_VOXELS / world
+    voxels per rank: the whole array, `output.npy`; above: `output_sample.npy`, the voxels at DUMP_VOXELS / world flat indices
+    drawn by RandomState(0).randint(0, size) and sorted (identical for identical arguments).  N > 1: one file per rank
+    (`_rank<r>` suffix), each rank's slab."""
+    os.makedirs(directory, exist_ok=True)
+    suffix = f'_rank{rank}' if world > 1 else ''
+    count = DUMP_VOXELS // world
+    if out.size <= count:
+        np.save(os.path.join(directory, f'output{suffix}.npy'), out.get())
+        return
+    idx = np.sort(np.random.RandomState(0).randint(0, out.size, size=count, dtype=np.int64))
+    plane = out.size // out.shape[0]
+    chunk = max(1, (64 << 20) // (4 * plane))            # planes per device-to-host copy: at most 64 MB of host memory
+    vals = np.empty(count, dtype=np.float32)
+    for d0 in range(0, out.shape[0], chunk):
+        d1 = min(out.shape[0], d0 + chunk)
+        lo, hi = np.searchsorted(idx, [d0 * plane, d1 * plane])
+        if hi > lo:
+            vals[lo:hi] = out.get_planes(d0, d1).reshape(-1)[idx[lo:hi] - d0 * plane]
+    np.save(os.path.join(directory, f'output_sample{suffix}.npy'), vals)
 
 
 def cpu_baseline(vol, interp, target_s, scipy_same_workload=True):
@@ -238,18 +272,22 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        sv.synchronize()
+        dump_outputs(out, args.dump_outputs, rank, world)
 
-    # per-angle distribution (after the timed region): the sweep's angles differ by +-10 % (footprint shape).  One event pair
-    # brackets `rep` back-to-back launches of the SAME angle, so the event pair's own cost and the launch gap (~17 us together,
-    # 8 % of a 0.2 ms launch: round 2's single-launch samples read above the mean of the timed region) are amortised.
-    rep = 8
-    step_ms = []
-    for i in range(min(args.steps, 180)):
-        sv.timer_start()
-        for _ in range(rep):
-            sv.affine(mats[args.warmup + i], output=out)
-        step_ms.append(sv.timer_stop() / rep)
-    step_ms = np.asarray(step_ms)
+    if args.full:
+        # per-angle distribution (after the timed region): the sweep's angles differ by +-10 % (footprint shape).  One event pair
+        # brackets `rep` back-to-back launches of the SAME angle, so the event pair's own cost and the launch gap (~17 us together,
+        # 8 % of a 0.2 ms launch: round 2's single-launch samples read above the mean of the timed region) are amortised.
+        rep = 8
+        step_ms = []
+        for i in range(min(args.steps, 180)):
+            sv.timer_start()
+            for _ in range(rep):
+                sv.affine(mats[args.warmup + i], output=out)
+            step_ms.append(sv.timer_stop() / rep)
+        step_ms = np.asarray(step_ms)
 
     info = sv.info()
     vox_per_step = nd * n * n * world
@@ -265,7 +303,18 @@ def main():
     kname = {1: f'vt::affine_direct<{kind_code}>', 2: f'vt::affine_tiled<{kind_code}', 3: f'vt::affine_tiled_zsep<{kind_code}',
              4: f'vt::affine_march_zsep<{kind_code}', 5: f'vt::affine_march_zpair<{kind_code}', 8: f'vt::affine_march4<{kind_code}'}.get(int(info.last_kernel), 'vt::affine')
     case = {(512, 'filt_bspline'): 'bench', (1024, 'filt_bspline'): 'sweep1024', (512, 'linear'): 'linear512', (1024, 'linear'): 'linear1024'}.get((n, interp))
-    traffic = measured_traffic('void ' + kname, case) if (case and world == 1) else None
+    traffic = measured_traffic('void ' + kname, case) if (args.full and case and world == 1) else None
+    roofline = {'bound': 'hbm', 'kernel': kname, 'achieved': round(achieved, 1), 'peak': 8000.0,
+                'unit': 'GB/s', 'frac': round(achieved / 8000.0, 4)}
+    if args.full:
+        roofline.update({'traffic': (round(traffic['bytes']) if traffic else None),
+                         'traffic_source': (traffic['source'] if traffic else None),
+                         'counters': (traffic['extra'] if traffic else None)})
+    roofline.update({'kernel_ms': round(kernel_ms, 4), 'algorithmic_bytes_per_launch': algo_bytes})
+    if args.full:
+        roofline['per_angle_ms'] = {'min': round(float(step_ms.min()), 4), 'median': round(float(np.median(step_ms)), 4),
+                                    'max': round(float(step_ms.max()), 4), 'mean': round(float(step_ms.mean()), 4),
+                                    'method': f'{rep} back-to-back launches of one angle per HIP event pair, after the timed region'}
     result = {
         'metric': f'Mvoxels/s, {n}^3 f32 {interp} StaticVolume transform (resident source, device output)',
         'value': round(value, 1), 'unit': 'Mvoxels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -279,15 +328,7 @@ def main():
                    # in-plane transposed copy): GPU time of those builds, once per handle, and everything resident now
                    'zfir_copy_ms_once': round(float(getattr(info, 'copies_ms', 0.0)), 3), 'resident_bytes': int(info.resident_bytes),
                    'angles': 'i' if args.steps >= 180 else f'round(i * 180 / {args.steps})'},
-        'roofline': {'bound': 'hbm', 'kernel': kname, 'achieved': round(achieved, 1), 'peak': 8000.0,
-                     'unit': 'GB/s', 'frac': round(achieved / 8000.0, 4),
-                     'traffic': (round(traffic['bytes']) if traffic else None),
-                     'traffic_source': (traffic['source'] if traffic else None),
-                     'counters': (traffic['extra'] if traffic else None),
-                     'kernel_ms': round(kernel_ms, 4), 'algorithmic_bytes_per_launch': algo_bytes,
-                     'per_angle_ms': {'min': round(float(step_ms.min()), 4), 'median': round(float(np.median(step_ms)), 4),
-                                      'max': round(float(step_ms.max()), 4), 'mean': round(float(step_ms.mean()), 4),
-                                      'method': f'{rep} back-to-back launches of one angle per HIP event pair, after the timed region'}},
+        'roofline': roofline,
     }
     if world > 1:
         # a first multi-GPU run should diagnose itself: every rank's own kernel time and halo time, not only the maximum
@@ -307,7 +348,7 @@ def main():
                                    'halo_planes': int(sv.halo), 'when': 'once, at SlabVolume construction (rank 0\'s bytes; max over ranks ms)',
                                    'backend': 'gloo (BENCH_ONE_GPU rehearsal)' if one_gpu else 'nccl (RCCL)'}
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # extra (not the headline): the linear kernel on the same volume, and the prefilter's own roofline
         extra = {}
         svl = vt.StaticVolume(vol, interpolation='linear', device=dev)
@@ -425,7 +466,7 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         # "throughput at 1/2/4/8 GPUs reported next to the CPU baseline timed on the same box's host cores" (north star): rank 0 times a
         # bounded sample of ITS slab's workload -- after the process group is gone, so that no rank sits in a collective while the host
         # works, and at N > 1 on a bounded crop of the slab (at most 256 planes cross PCIe and are prefiltered on the host, whatever the

@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -54,11 +55,29 @@ def test_bench_self_launch_ranks_share_one_gpu(world, strong):
 def test_bench_multirank_line_carries_the_cpu_baseline():
     """North star: "throughput at 1/2/4/8 GPUs reported next to the CPU baseline timed on the same box's host cores" -- the N > 1 line
     has `cpu_baseline` too (rank 0 times a bounded sample of its slab's workload; the 15 s scipy pass over the whole volume is N = 1 only)."""
-    args = ['--gpus', '2', '--size', '256', '--interp', 'bspline', '--steps', '5', '--warmup', '2', '--prewarm-ms', '0', '--cpu-seconds', '1']
+    args = ['--gpus', '2', '--size', '256', '--interp', 'bspline', '--steps', '5', '--warmup', '2', '--prewarm-ms', '0', '--cpu-seconds', '1',
+            '--full']
     r = run_bench(args, {'BENCH_ONE_GPU': '1'})
     cb = r['cpu_baseline']
     assert r['n_gpus'] == 2 and cb['value'] > 0 and cb['kind'] == 'port' and cb['cores'] >= 1 and cb['unit'] == 'Mvoxels/s'
     assert 'scipy_1thread' in cb and 'scipy_1thread_same_workload' not in cb
+
+
+def test_bench_plain_line_and_dumped_output_of_the_last_step(tmp_path):
+    """Without --full the line carries the headline and the timed region's roofline only; --dump-outputs writes what the LAST timed step
+    computed: at 128^3 the whole output, equal to the oracle's transform of the same seeded volume by the sweep's last angle."""
+    from oracle import oracle
+    from voltools_amd.utils import transform_matrix
+    n, steps = 128, 4
+    r = run_bench(['--gpus', '1', '--size', str(n), '--steps', str(steps), '--warmup', '2', '--prewarm-ms', '0',
+                   '--dump-outputs', str(tmp_path)])
+    assert r['steps'] == steps and r['ms_per_step'] > 0 and r['dtype'] == 'f32'
+    assert 'extra' not in r and 'cpu_baseline' not in r and 'per_angle_ms' not in r['roofline']
+    got = np.load(tmp_path / 'output.npy')
+    vol = np.random.RandomState(0).random_sample((n, n, n)).astype(np.float32)
+    centre = np.divide(np.subtract(vol.shape, 1), 2, dtype=np.float32)
+    m = transform_matrix(rotation=(0, 135.0, 0), rotation_units='deg', rotation_order='rzxz', center=centre)   # round(3 * 180 / 4)
+    assert got.shape == (n, n, n) and float(np.abs(got - oracle.affine(vol, m, 'filt_bspline')).max()) <= 3e-6
 
 
 def test_bench_device_generated_slabs():

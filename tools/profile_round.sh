@@ -34,9 +34,9 @@ profile() {   # name, then the python command line (the program itself follows `
 for c in $cases; do
   case $c in
     # (--no-extra-1024: the 1024^3 trilinear launches of `extra` would share a kernel-stats row with the 512^3 ones)
-    bench)         profile bench bench.py --steps 180 --warmup 5 --no-cpu-baseline --no-extra-1024 ;;
+    bench)         profile bench bench.py --steps 180 --warmup 5 --full --no-cpu-baseline --no-extra-1024 ;;
     linear512)     profile linear512 tools/prof_case.py --size 512 --interp linear --sweep 1 --iters 180 ;;     # BASELINE config #2
-    sweep1024)     profile sweep1024 bench.py --size 1024 --steps 60 --warmup 3 --no-cpu-baseline ;;
+    sweep1024)     profile sweep1024 bench.py --size 1024 --steps 60 --warmup 3 --full --no-cpu-baseline ;;
     linear1024)    profile linear1024 tools/prof_case.py --size 1024 --interp linear --sweep 6 --iters 30 ;;    # the north star's 1024^3 trilinear sweep
     general512)    profile general512_linear tools/prof_case.py --size 512 --interp linear --general --iters 30
                    profile general512_cubic tools/prof_case.py --size 512 --interp filt_bspline --general --iters 30 ;;
