@@ -99,7 +99,8 @@ typedef struct vt_volume_info {
     int32_t last_lds_bytes;
     int32_t last_grid;
     float   prefilter_ms;              /* one-time prefilter time measured at create (filt_*), else 0      */
-    uint64_t resident_bytes;           /* the plain resident copy and every lazily built one the handle holds now */
+    uint64_t resident_bytes;           /* what the budget counts: the plain resident copy, the projection helper, every lazily built
+                                          copy at the size of its allocation and the spare buffer kept for the next build */
     float   copies_ms;                 /* GPU time spent so far building lazy copies (relayouts; hip events on the handle's stream) */
     int32_t copies_built;              /* lazy copies built so far (rebuilt ones count again) */
     int32_t copies_evicted;            /* ... and released to stay inside the budget */

@@ -65,6 +65,41 @@ def test_budget_evicts_least_recently_used_and_changes_no_result(interp):
     tight.close()
 
 
+@pytest.mark.parametrize('offset', ['frac', 'int'])
+@pytest.mark.parametrize('interp', ['filt_bspline', 'bspline'])
+def test_axis2_exchange_path_under_a_budget(interp, offset):
+    """The axis-0 <-> 2 exchange path (cubic rotations about axis 2 whose axis-2 offset the row kernel declines: a fractional one, or any
+    under NO_ROWS) holds an exchanged-result buffer beside the exchanged copy and its plane-quad form.  The buffer is allocated first and
+    the later copies of the same call must never evict it (vt_resident.h: per-call pins).  At 2.6x the plain copy the exchanged copy does
+    not fit beside it and the call runs on a family on the plain layout; with room for the path's working set it marches, bit for bit
+    as an unbudgeted handle does."""
+    shape = (96, 100, 104)
+    vol = np.random.RandomState(11).random_sample(shape).astype(np.float32)
+    m = vt.utils.transform_matrix(rotation=(0, 0, 33), rotation_order='sxyz', center=centre(shape))
+    flags = _native.FORCE_TILED
+    if offset == 'frac':
+        m[2, 3] += 0.5
+    else:
+        flags |= _native.NO_ROWS
+    want = oracle.affine(vol, m, interp)
+    free = vt.StaticVolume(vol, interpolation=interp, device='gpu:0')
+    plain = free.info().resident_bytes
+    ref = free.affine(m, _flags=flags)
+    assert free.info().last_kernel == 8
+    for factor, marches in ((2.6, False), (3.5, True)):
+        budget = int(plain * factor)
+        sv = vt.StaticVolume(vol, interpolation=interp, device='gpu:0', max_resident_bytes=budget)
+        for i in range(3):
+            got = sv.affine(m, _flags=flags)
+            info = sv.info()
+            assert info.resident_bytes <= budget, (interp, offset, factor, i, info.resident_bytes, budget)
+            assert np.abs(got - want).max() <= TOL[interp], (interp, offset, factor, i, info.last_kernel)
+            if marches:
+                assert info.last_kernel == 8 and np.array_equal(got, ref), (interp, offset, i, info.last_kernel)
+        sv.close()
+    free.close()
+
+
 N = 1024
 
 

@@ -531,17 +531,13 @@ int run_prefilter(float* d_a, float* d_b, int D, int H, int W, int P, bool lo_in
 // Which resident copy a launch samples, and what is special about its output.
 struct Orientation {
     const float* src_plain = nullptr;  // plain-layout copy the launch (or its pair / quad relayout) is based on
-#ifdef VT_LEGACY
-    float** pair_slot = nullptr;       // where its plane-pair form lives (test build)
-#endif
-    float** quad_slot = nullptr;       // where its plane-quad form lives
-    float** quade_slot = nullptr;      // ... and the plane-quad form of its z-convolved volume (cubic launches with an integer axis-0 offset)
-    int quad_idx = 0;
+    int quad_idx = 0;                  // 0..3: plain, axes 0 <-> 1, in-plane transposed, axes 0 <-> 2 -- its plane-quad forms are the
+                                       // copies kCopyQ0 + quad_idx and (z-convolved) kCopyQe0 + quad_idx, its plane-pair form kCopyP0 + quad_idx
     int plain_id = -1;                 // LazyCopyId of the exchanged plain-layout copy this orientation is based on (-1: the handle's own plain copy);
                                        // built by ensure_secondary_copy only when the launch -- or the relayout of a missing quad form -- reads it
     int srcD = 0, srcH = 0;            // depth / height of that copy
     int rowW = 0, rowP = 0;            // row width / pitch of that copy
-    bool xswap = false;                // the kernels write an axis-0 <-> 2 exchanged result into d_tmp_x
+    bool xswap = false;                // the kernels write an axis-0 <-> 2 exchanged result into the copy kCopyTmpX
 };
 
 bool is_marching(int kind) { return kind == 4 || kind == 5 || kind == 8; }
@@ -574,132 +570,60 @@ vt_volume planning_view(const vt_volume* v, int D, int H, int W, int P, int oD, 
 // ---------------------------------------------------------------------------------------------------
 // lazily built resident copies: one place that allocates, times, budgets and evicts them
 // ---------------------------------------------------------------------------------------------------
-// A handle that has used every orientation holds up to 13 buffers besides its plain copy.  Round 5: they are built
-// through alloc_lazy(), which (1) keeps the handle inside its budget (vt_volume_set_max_resident / VT_MAX_RESIDENT_GB; the plain copy
-// counts) by releasing the least recently used copies first, (2) does the same once when hipMalloc fails without any budget -- a device
-// short of memory then trades an old orientation's copies for the new one instead of falling back to the slower family for good --, and
-// (3) never builds a copy that cannot fit the budget at all: the caller falls back to the family that reads the plain layout.
-enum LazyCopyId { kCopyT = 0, kCopyR, kCopyX, kCopyXe, kCopyQ0, kCopyQ1, kCopyQ2, kCopyQ3, kCopyQe0, kCopyQe1, kCopyQe2, kCopyQe3, kCopyTmpX, kCopyCount };
+// A handle that has used every orientation holds up to 13 buffers besides its plain copy.  They live in one table
+// (vt_resident.h), which decides what a build may evict; the functions below carry its decisions out on the device.  A copy that cannot
+// be built -- over the budget, or hipMalloc fails with nothing left to evict -- sends the caller to a family that reads the plain layout.
 
-float** lazy_slot(vt_volume* v, int id)
+float* copy_ptr(const vt_volume* v, int id) { return static_cast<float*>(v->lazy.copy[id].ptr); }
+
+// what the budget counts besides the lazy copies: the plain copy and the projection helper's
+uint64_t fixed_bytes(const vt_volume* v) { return v->src_bytes + (v->proj ? v->proj->src_bytes : 0); }
+uint64_t resident_now(const vt_volume* v) { return fixed_bytes(v) + v->lazy.held(); }
+
+// free what a decision of the table let go of, once no launch may still read it (an evicted buffer may be built over at once)
+void release(vt_volume* v, LazyCopies::Released& rel)
 {
-    switch (id) {
-        case kCopyT: return &v->d_src_t;
-        case kCopyR: return &v->d_src_r;
-        case kCopyX: return &v->d_src_x;
-        case kCopyXe: return &v->d_src_xe;
-        case kCopyQ0: return &v->d_src_q;
-        case kCopyQ1: return &v->d_src_t_q;
-        case kCopyQ2: return &v->d_src_r_q;
-        case kCopyQ3: return &v->d_src_x_q;
-        case kCopyQe0: case kCopyQe1: case kCopyQe2: case kCopyQe3: return &v->d_src_qe[id - kCopyQe0];
-        default: return &v->d_tmp_x;
-    }
+    if (rel.empty()) return;
+    (void)hipStreamSynchronize(v->stream);
+    for (void* b : rel.bufs) (void)hipFree(b);
+    (void)hipGetLastError();
+    v->copies_evicted += (int)rel.evicted.size();
+    if (std::getenv("VT_DEBUG_ALLOC"))
+        for (int id : rel.evicted)
+            std::fprintf(stderr, "[vt] evicted lazy copy %d (last used at launch %llu of %llu)\n", id,
+                         (unsigned long long)v->lazy.copy[id].used, (unsigned long long)v->lazy.use_clock);
+    rel = LazyCopies::Released();
 }
 
-uint64_t lazy_bytes(const vt_volume* v, int id)
+// a copy whose build failed (a zero-filled copy must never survive: later calls would sample it silently), or that is too small
+void discard_copy(vt_volume* v, int id)
 {
-    const uint64_t plain = (uint64_t)v->D * v->H * v->P * sizeof(float);
-    switch (id) {
-        case kCopyT: return v->d_src_t ? plain : 0;
-        case kCopyR: return v->d_src_r ? (uint64_t)v->D * v->W * v->Pr * sizeof(float) : 0;
-        case kCopyX: return v->d_src_x ? (uint64_t)v->W * v->H * v->Px * sizeof(float) : 0;
-        case kCopyXe: return v->d_src_xe ? plain : 0;
-        case kCopyQ0: case kCopyQ1: case kCopyQ2: case kCopyQ3: return v->quad_bytes[id - kCopyQ0];
-        case kCopyQe0: case kCopyQe1: case kCopyQe2: case kCopyQe3: return v->quade_bytes[id - kCopyQe0];
-        default: return v->d_tmp_x ? (uint64_t)v->tmp_x_elems * sizeof(float) : 0;
-    }
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(v->stream);                       // nothing may still be writing the buffer that is freed
+    (void)hipFree(v->lazy.forget(id));
+    (void)hipGetLastError();
 }
 
-uint64_t resident_now(const vt_volume* v)
+// Allocate lazy copy `id` (`bytes` large): hipSuccess, or hipErrorOutOfMemory when the budget or the device cannot hold it beside the
+// copies this call has touched.  `transient`: the copy the build reads, not counted against the budget (LazyCopies::make_room) -- the
+// budget bounds what a handle KEEPS; for the few milliseconds of a relayout the handle may hold that source beside it.
+hipError_t alloc_lazy(vt_volume* v, int id, size_t bytes, int transient = -1)
 {
-    uint64_t tot = (uint64_t)v->D * v->H * v->P * sizeof(float) + (v->proj ? (uint64_t)3 * v->proj->H * v->proj->P * sizeof(float) : 0);
-    for (int id = 0; id < kCopyCount; ++id) tot += lazy_bytes(v, id);
-    return tot + v->spare_bytes;
-}
-
-void drop_spare(vt_volume* v)
-{
-    if (v->spare) { (void)hipFree(v->spare); (void)hipGetLastError(); }
-    v->spare = nullptr; v->spare_bytes = 0;
-}
-
-void touch_lazy(vt_volume* v, int id) { if (id >= 0 && id < kCopyCount) v->copy_used[id] = v->use_clock; }
-
-// release the least recently used lazy copy that is none of keep_a / keep_b; false when there is none
-bool evict_lru(vt_volume* v, int keep_a, int keep_b)
-{
-    int victim = -1;
-    for (int id = 0; id < kCopyCount; ++id) {
-        if (id == keep_a || id == keep_b || !*lazy_slot(v, id)) continue;
-        if (victim < 0 || v->copy_used[id] < v->copy_used[victim]) victim = id;
-    }
-    if (victim < 0) return false;
-    (void)hipStreamSynchronize(v->stream);                        // no launch may still be reading what is released
-    float** s = lazy_slot(v, victim);
-    const size_t vbytes = (size_t)lazy_bytes(v, victim);
-    drop_spare(v);
-    v->spare = *s; v->spare_bytes = vbytes;                       // kept for the next build of that size (alloc_lazy); counted as resident
-    *s = nullptr;
-    if (victim >= kCopyQ0 && victim <= kCopyQ3) v->quad_bytes[victim - kCopyQ0] = 0;
-    if (victim >= kCopyQe0 && victim <= kCopyQe3) v->quade_bytes[victim - kCopyQe0] = 0;
-    if (victim == kCopyTmpX) v->tmp_x_elems = 0;
-    v->copies_evicted += 1;
-    if (std::getenv("VT_DEBUG_ALLOC")) std::fprintf(stderr, "[vt] evicted lazy copy %d (last used at launch %llu of %llu)\n", victim,
-                                                    (unsigned long long)v->copy_used[victim], (unsigned long long)v->use_clock);
-    return true;
-}
-
-// Allocate lazy copy `id` (`bytes` large) into its slot; keep_a / keep_b: copies this build reads or the launch needs.  hipSuccess, or
-// hipErrorOutOfMemory when the budget or the device cannot hold it (nothing is left half-built).
-// `transient`: a copy that only this build reads (the exchanged plain copy a plane-quad form is made from) and that is released right after
-// the build where the budget asks for it: it does not count against the budget while the build runs -- the budget bounds what a handle
-// KEEPS; for the few milliseconds of a relayout the handle may hold that source beside it (release_transient).
-hipError_t alloc_lazy(vt_volume* v, int id, size_t bytes, int keep_a, int keep_b, int transient = -1)
-{
-    float** slot = lazy_slot(v, id);
-    auto spare_fits = [&]() { return v->spare && v->spare_bytes >= bytes && v->spare_bytes - bytes <= bytes / 8; };
-    if (v->max_resident) {
-        const uint64_t leaving = transient >= 0 ? lazy_bytes(v, transient) : 0;
-        for (;;) {
-            const uint64_t held = resident_now(v) - leaving - (spare_fits() ? v->spare_bytes : 0);
-            if (held + bytes <= v->max_resident) break;
-            if (v->spare && !spare_fits()) { drop_spare(v); continue; }
-            if (!evict_lru(v, id == keep_a ? -1 : keep_a, keep_b)) return hipErrorOutOfMemory;        // does not fit the budget at all
-        }
-    }
-    if (spare_fits()) {
-        *slot = v->spare;
-        v->spare = nullptr; v->spare_bytes = 0;
-        touch_lazy(v, id);
-        return hipSuccess;
-    }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(slot), bytes);
+    LazyCopies::Released rel;
+    const bool fits = v->lazy.make_room(id, bytes, fixed_bytes(v), transient, rel);
+    release(v, rel);
+    if (!fits) return hipErrorOutOfMemory;
+    if (v->lazy.take_spare(id, bytes)) return hipSuccess;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
     while (e != hipSuccess) {
         (void)hipGetLastError();
-        *slot = nullptr;
-        if (v->spare) drop_spare(v);
-        else if (!evict_lru(v, keep_a, keep_b)) return hipErrorOutOfMemory;
-        e = hipMalloc(reinterpret_cast<void**>(slot), bytes);
+        if (!v->lazy.free_some(rel)) return hipErrorOutOfMemory;
+        release(v, rel);
+        e = hipMalloc(&p, bytes);
     }
-    touch_lazy(v, id);
+    v->lazy.record(id, p, bytes);
     return hipSuccess;
-}
-
-// after a build that read `transient`: back inside the budget, the build's source first
-void release_transient(vt_volume* v, int transient, int keep)
-{
-    if (!v->max_resident || resident_now(v) <= v->max_resident) return;
-    if (transient >= 0 && *lazy_slot(v, transient)) {
-        for (int id = 0; id < kCopyCount; ++id) if (id != transient && *lazy_slot(v, id) && v->copy_used[id] == 0) v->copy_used[id] = 1;
-        const uint64_t stamp = v->copy_used[transient];
-        v->copy_used[transient] = 0;                                  // the least recently used one by decree
-        if (!evict_lru(v, keep, -1)) v->copy_used[transient] = stamp;
-    }
-    while (resident_now(v) > v->max_resident) {
-        if (v->spare) { drop_spare(v); continue; }
-        if (!evict_lru(v, keep, -1)) break;
-    }
 }
 
 // GPU time of a copy's build, for vt_volume_info.copies_ms (events of their own: the handle's timer may be running)
@@ -721,33 +645,26 @@ void lazy_build_end(vt_volume* v)
 // The exchanged plain-layout copy of an orientation (kCopyT / kCopyR / kCopyX): 0 = it exists, 1 = it cannot be built.
 int ensure_lazy_plain(vt_volume* v, int id)
 {
-    float** slot = lazy_slot(v, id);
-    if (*slot) { touch_lazy(v, id); return 0; }
+    if (v->lazy.copy[id].ptr) { v->lazy.touch(id); return 0; }
     size_t bytes = 0;
     if (id == kCopyT) bytes = (size_t)v->D * v->H * v->P * sizeof(float);
     else if (id == kCopyR) { v->Pr = resident_pitch(v->H); bytes = (size_t)v->D * v->W * v->Pr * sizeof(float); }
     else if (id == kCopyX) { v->Px = resident_pitch(v->D); bytes = (size_t)v->W * v->H * v->Px * sizeof(float); }
     else return 1;
-    if (alloc_lazy(v, id, bytes, id, -1) != hipSuccess) { *slot = nullptr; return 1; }
+    if (alloc_lazy(v, id, bytes) != hipSuccess) return 1;
+    float* const dst = copy_ptr(v, id);
     lazy_build_begin(v);
     hipError_t e = hipSuccess;
     if (id == kCopyT) {
-        e = launch_relayout_swap01(v->d_src, v->d_src_t, v->D, v->H, v->P, v->stream);
+        e = launch_relayout_swap01(v->d_src, dst, v->D, v->H, v->P, v->stream);
     } else {
-        e = hipMemsetAsync(*slot, 0, bytes, v->stream);                                   // pad columns must be zero
+        e = hipMemsetAsync(dst, 0, bytes, v->stream);                                     // pad columns must be zero
         if (e == hipSuccess && id == kCopyR)        // dst[z][x][y]: element (i = y, j = z, k = x) -> (k = x, j = z, i = y)
-            e = launch_transpose02(v->d_src, v->d_src_r, v->H, v->D, v->W, v->P, (int64_t)v->H * v->P, v->Pr, (int64_t)v->W * v->Pr, v->stream);
+            e = launch_transpose02(v->d_src, dst, v->H, v->D, v->W, v->P, (int64_t)v->H * v->P, v->Pr, (int64_t)v->W * v->Pr, v->stream);
         else if (e == hipSuccess)
-            e = launch_transpose02(v->d_src, v->d_src_x, v->D, v->H, v->W, (int64_t)v->H * v->P, v->P, (int64_t)v->H * v->Px, v->Px, v->stream);
+            e = launch_transpose02(v->d_src, dst, v->D, v->H, v->W, (int64_t)v->H * v->P, v->P, (int64_t)v->H * v->Px, v->Px, v->stream);
     }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(v->stream);
-        (void)hipFree(*slot);
-        (void)hipGetLastError();
-        *slot = nullptr;
-        return 1;
-    }
+    if (e != hipSuccess) { discard_copy(v, id); return 1; }
     lazy_build_end(v);
     return 0;
 }
@@ -778,10 +695,7 @@ int try_axis1_exchange(vt_volume* v, const double m[12], int flags, size_t n_out
     *p = ps; *plan = plans;
     p->ostride = v->oW; p->orow = (int64_t)v->oH * v->oW;
     p->ord[0] = 1; p->ord[1] = 0; p->ord[2] = 2;          // original (d, h, w) = this launch's columns (1, 0, 2)
-    ori->src_plain = v->d_src_t; ori->plain_id = kCopyT; ori->quad_slot = &v->d_src_t_q; ori->quade_slot = &v->d_src_qe[1]; ori->quad_idx = 1;
-#ifdef VT_LEGACY
-    ori->pair_slot = &v->d_src_t_zp;
-#endif
+    ori->src_plain = copy_ptr(v, kCopyT); ori->plain_id = kCopyT; ori->quad_idx = 1;
     ori->srcD = v->H; ori->srcH = v->D;
     return 0;
 }
@@ -814,10 +728,7 @@ int try_axis2_exchange(vt_volume* v, const double m[12], int flags, size_t n_out
     v->Px = sw.P;
     *p = ps; *plan = plans;
     p->ord[0] = 2; p->ord[1] = 1; p->ord[2] = 0;          // original (d, h, w) = this launch's columns (2, 1, 0)
-    ori->src_plain = v->d_src_x; ori->plain_id = kCopyX; ori->quad_slot = &v->d_src_x_q; ori->quade_slot = &v->d_src_qe[3]; ori->quad_idx = 3;
-#ifdef VT_LEGACY
-    ori->pair_slot = &v->d_src_x_zp;
-#endif
+    ori->src_plain = copy_ptr(v, kCopyX); ori->plain_id = kCopyX; ori->quad_idx = 3;
     ori->srcD = v->W; ori->srcH = v->H; ori->rowW = v->D; ori->rowP = v->Px;
     ori->xswap = true;
     return 0;
@@ -844,10 +755,7 @@ int try_inplane_transposed(vt_volume* v, const double m[12], int flags, size_t n
     if (!is_marching(plans.kind)) return 0;
     v->Pr = sw.P;
     *p = ps; *plan = plans;
-    ori->src_plain = v->d_src_r; ori->plain_id = kCopyR; ori->quad_slot = &v->d_src_r_q; ori->quade_slot = &v->d_src_qe[2]; ori->quad_idx = 2;
-#ifdef VT_LEGACY
-    ori->pair_slot = &v->d_src_r_zp;
-#endif
+    ori->src_plain = copy_ptr(v, kCopyR); ori->plain_id = kCopyR; ori->quad_idx = 2;
     ori->srcD = v->D; ori->srcH = v->W; ori->rowW = v->H; ori->rowP = v->Pr;
     // Tile order on the transposed copy: h fastest for the round-1 marching kernels (consecutive tiles read neighbouring source
     // rows); the plane-quad kernel with its 2-D grid keeps w fastest -- [measured, angles 50..130] 1024^3 trilinear 1.58-1.70 ->
@@ -878,9 +786,9 @@ int try_general_reorient(vt_volume* v, const double m[12], int flags, size_t n_o
     if (c[0] > 1.15 * c[2] && c[0] > c[1]) a = 0;
     if (a == 2) return 0;
     if (a == 0 && !(v->plane0 == 0 && v->out_plane0 == 0 && v->gD == v->D)) return 0;  // slab windows live on axis 0: it stays the slowest
-    float** const slot = (a == 1) ? &v->d_src_r : &v->d_src_x;
+    const int id = (a == 1) ? kCopyR : kCopyX;
     int* const asked = &v->reorient_asked[a];
-    if (!*slot && ++*asked < ((flags & VT_FORCE_TILED) ? 1 : v->tune.reorient)) return 0;
+    if (!v->lazy.copy[id].ptr && ++*asked < ((flags & VT_FORCE_TILED) ? 1 : v->tune.reorient)) return 0;
     const vt_volume sw = (a == 1) ? planning_view(v, v->D, v->W, v->H, resident_pitch(v->H), v->oD, v->oH, v->oW, true)
                                   : planning_view(v, v->W, v->H, v->D, resident_pitch(v->D), v->oD, v->oH, v->oW, false);
     const int pi[3] = {a == 1 ? 0 : 2, a == 1 ? 2 : 1, a == 1 ? 1 : 0};                // source axis of the copy's axis r
@@ -893,12 +801,12 @@ int try_general_reorient(vt_volume* v, const double m[12], int flags, size_t n_o
     plan_launch(&sw, ms, flags, &ps, &plans);
     if (!(plans.kind == 2 || plans.kind == 6 || plans.kind == 9)) return 0;           // the general-matrix kernels only
     if (a == 1) v->Pr = sw.P; else v->Px = sw.P;
-    if (ensure_lazy_plain(v, a == 1 ? kCopyR : kCopyX)) {
+    if (ensure_lazy_plain(v, id)) {
         *asked = -64;                         // no room for another copy: the plain layout serves this matrix and the next 64 requests
         return 0;
     }
     *p = ps; *plan = plans;
-    ori->src_plain = *slot; ori->plain_id = a == 1 ? kCopyR : kCopyX;
+    ori->src_plain = copy_ptr(v, id); ori->plain_id = id;
     ori->srcD = sw.D; ori->srcH = sw.H; ori->rowW = sw.W; ori->rowP = sw.P;
     return 0;
 }
@@ -913,29 +821,23 @@ int try_rows(vt_volume* v, const double m[12], int flags, AffineParams* p, TileP
     plans.kind = 0;
     if (!plan_rows(v, m, flags, &ps, &plans) || plans.kind != 10) return 0;
     const bool use_xe = is_cubic(v->interp) && !(ps.flags & (1 << 16));      // (a fractional axis-2 offset forms its own x-sums on the plain copy)
-    if (use_xe && !v->d_src_xe) {
-        if (v->xe_retry_in > 0) { --v->xe_retry_in; return 0; }
-        const size_t bytes = (size_t)v->D * v->H * v->P * sizeof(float);
-        if (alloc_lazy(v, kCopyXe, bytes, kCopyXe, -1) != hipSuccess) {
-            v->d_src_xe = nullptr;            // no room for the copy: the exchange path or the general kernels serve this matrix
-            v->xe_retry_in = 64;
-            return 0;
-        }
+    LazyCopy& xe = v->lazy.copy[kCopyXe];
+    if (use_xe && !xe.ptr) {
+        // no room for the copy, or a refused relayout: the exchange path or the general kernels serve this matrix and the next 64
+        if (xe.retry_in > 0) { --xe.retry_in; return 0; }
+        if (alloc_lazy(v, kCopyXe, (size_t)v->D * v->H * v->P * sizeof(float)) != hipSuccess) { xe.retry_in = 64; return 0; }
         lazy_build_begin(v);
         const bool simple = v->interp == VT_BSPLINE_SIMPLE || v->interp == VT_FILT_BSPLINE_SIMPLE;
-        if (launch_relayout_xfir(v->d_src, v->d_src_xe, v->D, v->H, v->W, v->P, simple, v->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(v->stream);
-            (void)hipFree(v->d_src_xe);
-            v->d_src_xe = nullptr;
-            v->xe_retry_in = 64;
+        if (launch_relayout_xfir(v->d_src, copy_ptr(v, kCopyXe), v->D, v->H, v->W, v->P, simple, v->stream) != hipSuccess) {
+            discard_copy(v, kCopyXe);
+            xe.retry_in = 64;
             return 0;
         }
         lazy_build_end(v);
     }
     *p = ps; *plan = plans;
-    if (use_xe) touch_lazy(v, kCopyXe);
-    ori->src_plain = use_xe ? v->d_src_xe : v->d_src;
+    if (use_xe) v->lazy.touch(kCopyXe);
+    ori->src_plain = use_xe ? copy_ptr(v, kCopyXe) : v->d_src;
     return 0;
 }
 
@@ -949,105 +851,104 @@ void note_launch(vt_volume* v, int kind, const TilePlan& plan, const AffineParam
     v->last_grid = tiled ? plan.grid : (int)((n_out + 255) / 256);
 }
 
+// the exchanged-result buffer of an axis-0 <-> 2 launch holds its output
+bool xswap_buffer_ok(const vt_volume* v, size_t n_out)
+{
+    return v->lazy.copy[kCopyTmpX].ptr && v->lazy.copy[kCopyTmpX].bytes >= n_out * sizeof(float);
+}
+
 // Build the secondary resident copy a plan needs (once per handle and orientation).  Returns 0 when the copy exists, 1 when it
-// could not be built -- no device memory for it, or a relayout launch that was refused: the slot is freed and cleared (a zero-filled
-// copy must never survive: later calls would sample it silently) and the caller re-plans without this kernel family --, < 0 never.
+// could not be built -- no device memory for it, or a relayout launch that was refused: the copy is freed (a zero-filled copy must
+// never survive: later calls would sample it silently) and the caller re-plans without this kernel family --, < 0 never.
 int ensure_secondary_copy(vt_volume* v, const TilePlan& plan, const AffineParams& p, Orientation& ori)
 {
-    float** slot = nullptr;
     size_t bytes = 0;
     int id = -1;
     const bool zfir = plan.kind == 8 && (p.flags & (1 << 19)) != 0;       // the z-convolved copy (vt_plan.hip: plan_quad)
     if (plan.kind == 8) {
-        slot = zfir ? ori.quade_slot : ori.quad_slot;
         id = (zfir ? kCopyQe0 : kCopyQ0) + ori.quad_idx;
         bytes = (size_t)((ori.srcD + 3) / 4) * ori.srcH * p.sPq * sizeof(float);
 #ifdef VT_LEGACY
     } else if (plan.kind == 5) {
-        slot = ori.pair_slot;
+        id = kCopyP0 + ori.quad_idx;
         bytes = (size_t)((ori.srcD + 1) / 2) * ori.srcH * p.sP2 * sizeof(float);
 #endif
     }
-    // the exchanged result buffer of the axis-0 <-> 2 orientation
+    const bool built = id >= 0 && v->lazy.copy[id].ptr;
+    if (built) v->lazy.touch(id);              // (pinned before the result buffer below is allocated)
+    // the exchanged result buffer of the axis-0 <-> 2 orientation (allocated first: every copy built below is then sized against it)
+    const size_t n_out = (size_t)v->oD * v->oH * v->oW;
     if (ori.xswap) {
-        const size_t n_out = (size_t)v->oD * v->oH * v->oW;
-        if (v->tmp_x_elems < n_out) {
-            if (v->d_tmp_x) { (void)hipStreamSynchronize(v->stream); (void)hipFree(v->d_tmp_x); v->d_tmp_x = nullptr; v->tmp_x_elems = 0; }
-            if (alloc_lazy(v, kCopyTmpX, n_out * sizeof(float), kCopyTmpX, id) != hipSuccess) { v->d_tmp_x = nullptr; return 1; }
-            v->tmp_x_elems = n_out;
+        if (!xswap_buffer_ok(v, n_out)) {
+            if (v->lazy.copy[kCopyTmpX].ptr) discard_copy(v, kCopyTmpX);
+            if (alloc_lazy(v, kCopyTmpX, n_out * sizeof(float)) != hipSuccess) return 1;
         }
-        touch_lazy(v, kCopyTmpX);
+        v->lazy.touch(kCopyTmpX);
     }
-    if (slot && *slot) { touch_lazy(v, id); return 0; }                    // the launch reads this form only: its plain-layout source may be gone
+    // (every return of success below: what the launch reads is still there -- a mistake in the pins fails a call, it does not fault the GPU)
+    auto ready = [&] { return ori.xswap && !xswap_buffer_ok(v, n_out) ? 1 : 0; };
+    if (built) return ready();                 // the launch reads this form only: its plain-layout source may be gone
     // The exchanged plain-layout copy of the orientation: read by the launch itself (kinds that sample the plain layout) or by the relayout
     // that builds the missing plane-quad form.  Built here and not when the orientation is chosen: under a budget it is the first copy
     // evicted once its quad form exists, and a sweep must not rebuild it on every call.
     // (Round 5: the plane-quad forms of the in-plane transposed orientation come straight from the handle's own plain copy --
     // relayout_zquad_swap12 -- when that exchanged copy does not exist yet: nothing else reads it on this path.)
-    const bool fused_swap12 = plan.kind == 8 && ori.plain_id == kCopyR && !v->d_src_r && !v->tune.no_fused_relayout;
-    if (ori.plain_id >= 0 && !fused_swap12) {
-        if (ensure_lazy_plain(v, ori.plain_id)) return 1;
-        ori.src_plain = *lazy_slot(v, ori.plain_id);
+    const bool fused_swap12 = plan.kind == 8 && ori.plain_id == kCopyR && !v->lazy.copy[kCopyR].ptr && !v->tune.no_fused_relayout;
+    const int transient = fused_swap12 ? -1 : ori.plain_id;
+    if (transient >= 0) {
+        if (ensure_lazy_plain(v, transient)) return 1;
+        ori.src_plain = copy_ptr(v, transient);
     }
-    if (!slot) return 0;
+    if (id < 0) return ready();
 #ifdef VT_LEGACY
     if (v->tune.test_fail_copy) return 1;      // VT_TEST_FAIL_COPY (test build): the allocation-failure path, for tests/test_gpu_parity.py
 #endif
     // A copy that did not fit is not attempted again at once: a device that is short of memory would pay a volume-sized hipMalloc
     // (and its failure) on every call.  The next attempt comes kCopyRetryCalls calls later.
     constexpr int kCopyRetryCalls = 64;
-    int* const retry = (plan.kind == 8) ? &v->copy_retry_in[ori.quad_idx + (zfir ? 4 : 0)] : nullptr;
-    if (retry && *retry > 0) { --*retry; return 1; }
-    hipError_t e = hipSuccess;
-    if (id >= 0) e = alloc_lazy(v, id, bytes, id, fused_swap12 ? -1 : ori.plain_id, fused_swap12 ? -1 : ori.plain_id);
-    else e = hipMalloc(reinterpret_cast<void**>(slot), bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();              // no room for another copy of the volume: a family that reads the plain layout serves the call
-        *slot = nullptr;
-        if (retry) *retry = kCopyRetryCalls;
+    int& retry = v->lazy.copy[id].retry_in;
+    if (retry > 0) { --retry; return 1; }
+    if (alloc_lazy(v, id, bytes, transient) != hipSuccess) {
+        retry = kCopyRetryCalls;               // no room for another copy of the volume: a family that reads the plain layout serves the call
         return 1;
     }
+    float* const dst = copy_ptr(v, id);
     lazy_build_begin(v);
-    if (plan.kind != 8) e = hipMemsetAsync(*slot, 0, bytes, v->stream);       // positions beyond the row's width stay zero (the plane-quad relayouts write them themselves)
+    hipError_t e = hipSuccess;
+    if (plan.kind != 8) e = hipMemsetAsync(dst, 0, bytes, v->stream);         // positions beyond the row's width stay zero (the plane-quad relayouts write them themselves)
     if (e == hipSuccess) {
         if (fused_swap12)
-            e = launch_relayout_zquad_swap12(v->d_src, *slot, v->D, v->H, v->W, v->P, p.sPq, zfir, (p.flags & (1 << 18)) != 0, v->stream);
+            e = launch_relayout_zquad_swap12(v->d_src, dst, v->D, v->H, v->W, v->P, p.sPq, zfir, (p.flags & (1 << 18)) != 0, v->stream);
         else if (zfir)
-            e = launch_relayout_zquad_fir(ori.src_plain, *slot, ori.srcD, ori.srcH, ori.rowW, ori.rowP, p.sPq, (p.flags & (1 << 18)) != 0, v->stream);
+            e = launch_relayout_zquad_fir(ori.src_plain, dst, ori.srcD, ori.srcH, ori.rowW, ori.rowP, p.sPq, (p.flags & (1 << 18)) != 0, v->stream);
         else if (plan.kind == 8)
-            e = launch_relayout_zquad(ori.src_plain, *slot, ori.srcD, ori.srcH, ori.rowW, ori.rowP, p.sPq, v->stream);
+            e = launch_relayout_zquad(ori.src_plain, dst, ori.srcD, ori.srcH, ori.rowW, ori.rowP, p.sPq, v->stream);
 #ifdef VT_LEGACY
         else
-            e = launch_relayout_zpair(ori.src_plain, *slot, ori.srcD, ori.srcH, ori.rowW, ori.rowP, p.sP2, v->stream);
+            e = launch_relayout_zpair(ori.src_plain, dst, ori.srcD, ori.srcH, ori.rowW, ori.rowP, p.sP2, v->stream);
 #endif
     }
     if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(v->stream);                       // nothing may still be writing the buffer that is freed
-        (void)hipFree(*slot);
-        (void)hipGetLastError();
-        *slot = nullptr;
-        if (retry) *retry = kCopyRetryCalls;
+        discard_copy(v, id);
+        retry = kCopyRetryCalls;
         return 1;
     }
     lazy_build_end(v);
-    if (zfir) v->quade_bytes[ori.quad_idx] = bytes;
-    else if (plan.kind == 8) v->quad_bytes[ori.quad_idx] = bytes;
-    if (id >= 0) release_transient(v, fused_swap12 ? -1 : ori.plain_id, id);             // (lazy_build_end has waited for the relayout: its source may go)
-    if (std::getenv("VT_DEBUG_ALLOC")) std::fprintf(stderr, "[vt] secondary copy kind %d orientation %d at %p, %zu bytes (plain source %p)\n", plan.kind, ori.quad_idx, (void*)*slot, bytes, (const void*)ori.src_plain);
-    if (zfir) v->quade_bytes[ori.quad_idx] = bytes;
-    else if (plan.kind == 8) v->quad_bytes[ori.quad_idx] = bytes;
-#ifdef VT_LEGACY
-    else v->P2 = p.sP2;
-#endif
-    return 0;
+    {   // (lazy_build_end has waited for the relayout: its source may go)
+        LazyCopies::Released rel;
+        v->lazy.trim(fixed_bytes(v), transient, rel);
+        release(v, rel);
+    }
+    if (std::getenv("VT_DEBUG_ALLOC")) std::fprintf(stderr, "[vt] secondary copy kind %d orientation %d at %p, %zu bytes (plain source %p)\n", plan.kind, ori.quad_idx, (void*)dst, bytes, (const void*)ori.src_plain);
+    return ready();
 }
 
 // launch the plan's kernel into d_out (the secondary copy it reads exists: ensure_secondary_copy)
 int launch_planned(vt_volume* v, const TilePlan& plan, const AffineParams& p, const Orientation& ori, float* d_out, size_t n_out)
 {
+    if (ori.xswap && !xswap_buffer_ok(v, n_out)) return fail(VT_EINVAL, "internal: exchanged-result copy missing");
     if (plan.kind == 8) {
-        float* const srcq = (p.flags & (1 << 19)) ? *ori.quade_slot : *ori.quad_slot;
+        float* const srcq = copy_ptr(v, ((p.flags & (1 << 19)) ? kCopyQe0 : kCopyQ0) + ori.quad_idx);
         if (!srcq) return fail(VT_EINVAL, "internal: plane-quad copy missing");
         // Every other launch of a handle walks the chunk layers from the last to the first: the source planes the previous launch
         // read last are still in the memory-side cache (256 MB, it sees reads and writes alike) when this one starts with them.
@@ -1063,8 +964,9 @@ int launch_planned(vt_volume* v, const TilePlan& plan, const AffineParams& p, co
         VT_HIP(launch_affine_quad(plan.cfg, v->interp, srcq, d_out, q, plan.grid, plan.lds_bytes, v->stream));
 #ifdef VT_LEGACY
     } else if (plan.kind == 5) {
-        if (!*ori.pair_slot) return fail(VT_EINVAL, "internal: plane-pair copy missing");
-        VT_HIP(launch_affine_zpair(plan.cfg, v->interp, *ori.pair_slot, d_out, p, plan.grid, plan.lds_bytes, v->stream));
+        float* const srcp = copy_ptr(v, kCopyP0 + ori.quad_idx);
+        if (!srcp) return fail(VT_EINVAL, "internal: plane-pair copy missing");
+        VT_HIP(launch_affine_zpair(plan.cfg, v->interp, srcp, d_out, p, plan.grid, plan.lds_bytes, v->stream));
 #endif
     } else if (plan.kind == 9 || plan.kind == 6) {
         if (!v->d_queue) {                                           // tile counters of the persistent kernels: zero between launches
@@ -1128,7 +1030,11 @@ int do_affine(vt_volume* v, const double m4x4[16], float* out, int flags)
     TilePlan plan;
     Orientation ori;
     const size_t n_out = (size_t)v->oD * v->oH * v->oW;
-    v->use_clock += 1;
+    struct CallPins {                             // the copies this call touches are pinned until it returns (vt_resident.h)
+        LazyCopies& lazy;
+        explicit CallPins(LazyCopies& l) : lazy(l) { lazy.begin_call(); }
+        ~CallPins() { lazy.end_call(); }
+    } pins(v->lazy);
     // Plan, then make sure the resident copy the plan reads exists.  A copy that cannot be built (device memory: a handle that has
     // used every orientation holds up to 8 copies of its volume) takes its kernel family out of the running and the call is
     // planned again: quad -> pair (cubic) / plain marching -> ... every family from kind 4 down reads the plain layout.
@@ -1138,10 +1044,7 @@ int do_affine(vt_volume* v, const double m4x4[16], float* out, int flags)
         plan = TilePlan();
         plan.kind = 0;
         ori = Orientation();
-        ori.src_plain = v->d_src; ori.quad_slot = &v->d_src_q; ori.quade_slot = &v->d_src_qe[0]; ori.quad_idx = 0;
-#ifdef VT_LEGACY
-        ori.pair_slot = &v->d_src_zp;
-#endif
+        ori.src_plain = v->d_src;
         ori.srcD = v->D; ori.srcH = v->H; ori.rowW = v->W; ori.rowP = v->P;
         const int pf = flags | deny;
         // single-axis rotations about axes 1 / 2 and in-plane maps near a quarter turn march on an exchanged resident copy
@@ -1170,10 +1073,10 @@ int do_affine(vt_volume* v, const double m4x4[16], float* out, int flags)
             VT_HIP(pin.copy(d_out, out, n_out * sizeof(float), hipMemcpyHostToDevice, v->stream));
     }
     float* const d_final = d_out;
-    if (ori.xswap) d_out = v->d_tmp_x;            // the kernels write the exchanged result [w][h][d]
+    if (ori.xswap) d_out = copy_ptr(v, kCopyTmpX);       // the kernels write the exchanged result [w][h][d]
     if ((rc = launch_planned(v, plan, p, ori, d_out, n_out))) return rc;
     if (ori.xswap)                                // [w][h][d] -> [d][h][w]
-        VT_HIP(launch_transpose02(v->d_tmp_x, d_final, v->oW, v->oH, v->oD, (int64_t)v->oH * v->oD, v->oD,
+        VT_HIP(launch_transpose02(d_out, d_final, v->oW, v->oH, v->oD, (int64_t)v->oH * v->oD, v->oD,
                                   (int64_t)v->oH * v->oW, v->oW, v->stream));
     if (host_out) {
         VT_HIP(pin.copy(out, d_final, n_out * sizeof(float), hipMemcpyDeviceToHost, v->stream));
@@ -1253,7 +1156,7 @@ int create_common(int dev, int D, int H, int W, int interp, const float* data, i
     v->plane0 = plane0; v->gD = gD; v->out_plane0 = out_plane0;
     v->edge_pad = pad;
     v->tune.read();
-    if (v->tune.max_resident_gb > 0.0) v->max_resident = (uint64_t)(v->tune.max_resident_gb * 1073741824.0);
+    if (v->tune.max_resident_gb > 0.0) v->lazy.max_resident = (uint64_t)(v->tune.max_resident_gb * 1073741824.0);
 
     auto cleanup = [&](int code) {
         vt_volume_destroy(v);
@@ -1912,23 +1815,11 @@ int vt_volume_destroy(vt_volume_t* v)
     if (v->stream) hipStreamSynchronize(v->stream);
     if (v->d_src) cached_free(v->dev, v->d_src, v->src_bytes);
     if (v->d_queue) hipFree(v->d_queue);
-#ifdef VT_LEGACY
-    if (v->d_src_zp) hipFree(v->d_src_zp);
-    if (v->d_src_t_zp) hipFree(v->d_src_t_zp);
-    if (v->d_src_r_zp) hipFree(v->d_src_r_zp);
-    if (v->d_src_x_zp) hipFree(v->d_src_x_zp);
-#endif
-    if (v->d_src_t) hipFree(v->d_src_t);
-    if (v->d_src_x) hipFree(v->d_src_x);
-    if (v->d_src_r) hipFree(v->d_src_r);
-    if (v->d_src_q) hipFree(v->d_src_q);
-    if (v->d_src_t_q) hipFree(v->d_src_t_q);
-    if (v->d_src_r_q) hipFree(v->d_src_r_q);
-    if (v->d_src_x_q) hipFree(v->d_src_x_q);
-    for (int i = 0; i < 4; ++i) if (v->d_src_qe[i]) hipFree(v->d_src_qe[i]);
-    if (v->d_src_xe) hipFree(v->d_src_xe);
-    if (v->d_tmp_x) hipFree(v->d_tmp_x);
-    if (v->spare) hipFree(v->spare);
+    {
+        LazyCopies::Released rel;
+        v->lazy.release_all(rel);
+        for (void* b : rel.bufs) hipFree(b);
+    }
     if (v->d_scratch_out) cached_free(v->dev, v->d_scratch_out, v->scratch_elems * sizeof(float));
     if (v->d_proj_tmp) hipFree(v->d_proj_tmp);
     if (v->d_batch_m) hipFree(v->d_batch_m);
@@ -1943,30 +1834,20 @@ int vt_volume_destroy(vt_volume_t* v)
 }
 
 // Free every resident copy a handle has built lazily besides its plain one (exchanged orientations, plane-quad and z-convolved
-// plane-quad forms, the exchanged-result buffer).  They are rebuilt by the first call that needs them; results do not change.
+// plane-quad forms, the exchanged-result buffer) and the spare; `freed_bytes` is their sum.  They are rebuilt by the first call that
+// needs them; results do not change.
 int vt_volume_release_copies(vt_volume_t* v, uint64_t* freed_bytes)
 {
     if (!v) return fail(VT_EINVAL, "NULL argument");
     int rc = use_device(v->dev);
     if (rc) return rc;
-    vt_volume_info_t before, after;
-    if ((rc = vt_volume_info(v, &before))) return rc;
     VT_HIP(hipStreamSynchronize(v->stream));      // no launch may still be reading what is freed
-    float** const slots[] = {&v->d_src_t, &v->d_src_x, &v->d_src_r, &v->d_src_q, &v->d_src_t_q, &v->d_src_r_q, &v->d_src_x_q,
-                             &v->d_src_qe[0], &v->d_src_qe[1], &v->d_src_qe[2], &v->d_src_qe[3], &v->d_tmp_x, &v->d_src_xe,
-#ifdef VT_LEGACY
-                             &v->d_src_zp, &v->d_src_t_zp, &v->d_src_r_zp, &v->d_src_x_zp,
-#endif
-    };
-    for (float** s : slots)
-        if (*s) { VT_HIP(hipFree(*s)); *s = nullptr; }
-    drop_spare(v);
-    v->tmp_x_elems = 0;
-    for (int i = 0; i < 4; ++i) { v->quad_bytes[i] = 0; v->quade_bytes[i] = 0; }
-    for (int i = 0; i < 8; ++i) v->copy_retry_in[i] = 0;      // memory was just returned: a copy that did not fit may fit now
-    v->xe_retry_in = 0;
-    if ((rc = vt_volume_info(v, &after))) return rc;
-    if (freed_bytes) *freed_bytes = before.resident_bytes - after.resident_bytes;
+    LazyCopies::Released rel;
+    const uint64_t freed = v->lazy.release_all(rel);
+    hipError_t e = hipSuccess;
+    for (void* b : rel.bufs) if (hipError_t eb = hipFree(b)) e = eb;
+    VT_HIP(e);
+    if (freed_bytes) *freed_bytes = freed;
     return 0;
 }
 
@@ -1990,45 +1871,31 @@ int vt_volume_info(const vt_volume_t* v, vt_volume_info_t* info)
     for (int i = 0; i < 3; ++i) { info->last_tile[i] = v->last_tile[i]; info->last_lds_dims[i] = v->last_lds[i]; }
     info->last_lds_bytes = v->last_lds_bytes; info->last_grid = v->last_grid;
     info->prefilter_ms = v->prefilter_ms;
-    const uint64_t plain = (uint64_t)v->D * v->H * v->P * sizeof(float);
-    info->resident_bytes = plain + (v->d_src_t ? plain : 0) + (v->d_src_xe ? plain : 0) +
-                           (v->proj ? (uint64_t)3 * v->proj->H * v->proj->P * sizeof(float) : 0) +
-                           (v->d_src_r ? (uint64_t)v->D * v->W * v->Pr * sizeof(float) : 0) +
-                           (v->d_src_x ? (uint64_t)v->W * v->H * v->Px * sizeof(float) : 0) +
-                           (v->d_tmp_x ? (uint64_t)v->tmp_x_elems * sizeof(float) : 0) +
-                           v->quad_bytes[0] + v->quad_bytes[1] + v->quad_bytes[2] + v->quad_bytes[3] +
-                           v->quade_bytes[0] + v->quade_bytes[1] + v->quade_bytes[2] + v->quade_bytes[3];
-#ifdef VT_LEGACY
-    info->resident_bytes += (v->d_src_zp ? (uint64_t)((v->D + 1) / 2) * v->H * v->P2 * sizeof(float) : 0) +
-                            (v->d_src_t_zp ? (uint64_t)((v->H + 1) / 2) * v->D * v->P2 * sizeof(float) : 0) +
-                            (v->d_src_r_zp ? (uint64_t)((v->D + 1) / 2) * v->W * v->P2 * sizeof(float) : 0) +
-                            (v->d_src_x_zp ? (uint64_t)((v->W + 1) / 2) * v->H * v->P2 * sizeof(float) : 0);
-#endif
+    info->resident_bytes = resident_now(v);
     info->copies_ms = v->copies_ms;
     info->copies_built = v->copies_built;
     info->copies_evicted = v->copies_evicted;
-    info->max_resident_bytes = v->max_resident;
+    info->max_resident_bytes = v->lazy.max_resident;
     return 0;
 }
 
 // Resident-memory budget of a handle (round 5; no reference counterpart: the reference keeps one CUDA array per StaticVolume,
-// volume.py:37-45).  `bytes` counts the plain resident copy and every lazily built one; 0 = no limit (the default unless
-// VT_MAX_RESIDENT_GB is set).  A copy that would take the handle over its budget is built only after the least recently used lazy copies
-// have been released; one that cannot fit at all is not built, and the call runs on the kernel family that samples the plain layout.
-// A budget below the handle's present footprint releases copies at once.  Results never depend on the budget.
+// volume.py:37-45).  `bytes` counts what vt_volume_info.resident_bytes counts: the plain resident copy, the projection helper, every
+// lazily built copy at the size of its allocation and the spare; 0 = no limit (the default unless VT_MAX_RESIDENT_GB is set).  The rules
+// (vt_resident.h): a copy that would take the handle over its budget is built only after the least recently used copies have been
+// released, never one the same call has touched (per-call pins); a copy that cannot fit beside the plain copy and the pinned ones is
+// refused before anything is released, and the call runs on a kernel family that samples the plain layout.  A budget below the
+// handle's present footprint releases copies at once (this runs outside a call: nothing is pinned).  Results never depend on the budget.
 int vt_volume_set_max_resident(vt_volume_t* v, uint64_t bytes)
 {
     if (!v) return fail(VT_EINVAL, "NULL argument");
     int rc = use_device(v->dev);
     if (rc) return rc;
-    v->max_resident = bytes;
-    if (bytes)
-        while (resident_now(v) > bytes) {
-            if (v->spare) { drop_spare(v); continue; }
-            if (!evict_lru(v, -1, -1)) break;         // (the plain copy alone may exceed a tiny budget: it stays)
-        }
-    for (int i = 0; i < 8; ++i) v->copy_retry_in[i] = 0;
-    v->xe_retry_in = 0;
+    v->lazy.max_resident = bytes;
+    LazyCopies::Released rel;
+    v->lazy.trim(fixed_bytes(v), -1, rel);       // (outside a call: nothing is pinned)
+    release(v, rel);
+    v->lazy.clear_retries();
     return 0;
 }
 

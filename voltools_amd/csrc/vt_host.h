@@ -1,6 +1,7 @@
 // vt_host.h -- host-side declarations shared by the C ABI (vt_api.hip) and the launch planner (vt_plan.hip).
 #pragma once
 #include "vt_internal.h"
+#include "vt_resident.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -121,41 +122,13 @@ struct vt_volume {
     float* d_src = nullptr;
     size_t src_bytes = 0;              // size of the d_src allocation (small ones are recycled per device)
     float* d_zeros = nullptr;          // 16 bytes of zeros: the border fetch target of the tiled kernel
-    float* d_src_t = nullptr;          // resident copy with axes 0 and 1 exchanged (rotations about axis 1 march along it); lazy
-    float* d_src_r = nullptr;          // resident copy transposed in-plane ([z][x][y], pitch Pr; quarter-turn class of in-plane maps); lazy
-    int Pr = 0;
-    float* d_src_x = nullptr;          // resident copy with axes 0 and 2 exchanged ([x][y][z], pitch Px; rotations about axis 2); lazy
+    int Pr = 0;                        // row pitch of the in-plane transposed copy (kCopyR) and of the axis-0 <-> 2 exchanged one (kCopyX)
     int Px = 0;
-    float* d_tmp_x = nullptr;          // exchanged result of an axis-2 launch, before it is turned back
-    size_t tmp_x_elems = 0;
-    float* d_src_q = nullptr;          // plane-quad copies ([z/4][y][x][4]; vt_kernels_quad.hip) of the four orientations; lazy
-    float* d_src_t_q = nullptr;
-    float* d_src_r_q = nullptr;
-    float* d_src_x_q = nullptr;
-    size_t quad_bytes[4] = {0, 0, 0, 0};   // allocation sizes of the four quad copies (vt_volume_info)
-    float* d_src_xe = nullptr;         // plain-layout copy convolved along axis 2 with the cubic weights of fraction 0 (row kernel, kind 10, cubic; vt_kernels_rows.hip: relayout_xfir); lazy
-    float* d_src_qe[4] = {nullptr, nullptr, nullptr, nullptr};   // plane-quad copies of the Z-CONVOLVED volume per orientation (cubic launches with an integer axis-0 offset; vt_kernels_quad.hip: relayout_zquad_fir); lazy
-    size_t quade_bytes[4] = {0, 0, 0, 0};
     int reorient_asked[3] = {0, 0, 0};   // general matrices that asked for the copy whose fastest axis is source axis 0 / 1 (vt_api.hip: try_general_reorient)
-    int xe_retry_in = 0;               // calls to go before the x-convolved copy is attempted again after an allocation failure
-    int copy_retry_in[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // calls to go before a quad copy that could not be allocated is attempted again (per orientation; 4..7: the z-convolved ones)
-#ifdef VT_LEGACY
-    // plane-pair copies of the four orientations (round 1's cubic marching kernel, kind 5): test build only
-    float* d_src_zp = nullptr;
-    float* d_src_t_zp = nullptr;
-    float* d_src_r_zp = nullptr;
-    float* d_src_x_zp = nullptr;
-    int P2 = 0;                        // floats per pair-row of d_src_zp
-#endif
-    // lazily built resident copies: budget, least-recently-used eviction, build time (vt_api.hip: lazy copies)
-    uint64_t max_resident = 0;         // bytes this handle may keep resident, plain copy included (0 = no limit); vt_volume_set_max_resident / VT_MAX_RESIDENT_GB
-    uint64_t use_clock = 0;            // launches so far
-    uint64_t copy_used[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // launch that last read copy i (LazyCopyId)
+    vt::LazyCopies lazy;               // the lazily built resident copies, their budget and the spare (vt_resident.h)
     float copies_ms = 0.f;             // GPU time spent building lazy copies so far
     int copies_built = 0, copies_evicted = 0;
     hipEvent_t evc0 = nullptr, evc1 = nullptr;
-    float* spare = nullptr;            // the buffer of the lazy copy evicted last, kept for the next build of that size (a sweep under a budget
-    size_t spare_bytes = 0;            // trades one orientation's copy for another's: no hipFree + hipMalloc of gigabytes per switch)
     int* d_queue = nullptr;            // lane-block kernel: tile counters (one per XCD + a departure count), zero between launches
     float* d_scratch_out = nullptr;    // staging for host outputs
     double* d_batch_m = nullptr;       // batch launches: n x 12 folded matrices
