@@ -1,5 +1,6 @@
 """Cycle counts of the plane-quad kernel's set-up phases (experiment build, VT_EXP_NOLOOP=1: thread 0 of every workgroup leaves four
-clock64() differences in the output buffer): geometry | span atomics | placement by wave 0 | vector offsets.
+clock64() differences in the output buffer): geometry | span atomics | placement by wave 0 | vector offsets.  A workgroup of KIND 4 that
+loads its tile's shared plan leaves 0 cycles of placement (its plan load and vote count as span atomics).
     VT_LIB=.../lib_b/libvoltools_hip.so VT_EXP_NOLOOP=1 python3 tools/setup_phases.py --size 512 --interp filt_bspline --angle 30"""
 import argparse, os, sys
 import numpy as np
@@ -26,3 +27,6 @@ st = host.reshape(-1)[:4 * g].reshape(g, 4)
 print(f'{a.interp} {n}^3 angle {a.angle}: kernel {info.last_kernel} grid {g}; mean cycles per workgroup: geometry {st[:,0].mean():.0f}, '
       f'atomics {st[:,1].mean():.0f}, placement {st[:,2].mean():.0f}, offsets {st[:,3].mean():.0f}; total {st.sum(1).mean():.0f} '
       f'(median {np.median(st.sum(1)):.0f})')
+# workgroups of tiles outside the source return before the first stamp and leave their four floats at 0
+run = st.sum(1) > 0
+print(f'  workgroups past the set-up: {run.sum()} of {g}; shared-plan hits (placement phase of 0 cycles): {(st[run, 2] == 0).mean() * 100:.1f} %')

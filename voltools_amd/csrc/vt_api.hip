@@ -956,6 +956,23 @@ int launch_planned(vt_volume* v, const TilePlan& plan, const AffineParams& p, co
         // last to first -- the control, which measures like 0.)
         AffineParams q = p;
         if (v->tune.quad_pingpong == 2 || (v->tune.quad_pingpong == 1 && ((v->launch_no++) & 1))) q.flags |= (1 << 20);
+        // KIND 4 (plan_quad set bit 17): one plan slot per in-plane tile, a new epoch per launch.  A granule left by an earlier launch
+        // carries an older epoch and is ignored, so nothing is cleared between launches; the buffer is per handle like its stream.
+        if (q.flags & (1 << 17)) {
+            const size_t need = (size_t)q.nTh * q.nTw * quad_tile_plan_granules(plan.cfg) * 16;
+            if (v->tplan_bytes < need) {
+                if (v->d_tplan) { VT_HIP(hipFree(v->d_tplan)); v->d_tplan = nullptr; v->tplan_bytes = 0; }
+                VT_HIP(hipMalloc(&v->d_tplan, need));
+                v->tplan_bytes = need;
+                v->tplan_epoch = 0;
+            }
+            if (v->tplan_epoch == 0 || v->tplan_epoch == 0xffffffffu) {      // new buffer, or the epochs wrapped: start from zeros again
+                VT_HIP(hipMemsetAsync(v->d_tplan, 0, v->tplan_bytes, v->stream));
+                v->tplan_epoch = 0;
+            }
+            q.tplan = v->d_tplan;
+            q.tplan_epoch = ++v->tplan_epoch;
+        }
         // (Round 5 measured per-launch TILE TABLES here -- the in-plane set-up of every tile worked out once, by a one-layer pass of the same
         //  kernel in front of the real launch, and read back by every chunk layer: bit-identical, the real launch faster and flatter over the
         //  angles, but the pass itself sits in front of every launch with 12-14 us, twice what it saves: 512^3 filt_bspline sweep 0.1983 ms
@@ -1815,6 +1832,7 @@ int vt_volume_destroy(vt_volume_t* v)
     if (v->stream) hipStreamSynchronize(v->stream);
     if (v->d_src) cached_free(v->dev, v->d_src, v->src_bytes);
     if (v->d_queue) hipFree(v->d_queue);
+    if (v->d_tplan) hipFree(v->d_tplan);
     {
         LazyCopies::Released rel;
         v->lazy.release_all(rel);

@@ -130,6 +130,9 @@ struct vt_volume {
     int copies_built = 0, copies_evicted = 0;
     hipEvent_t evc0 = nullptr, evc1 = nullptr;
     int* d_queue = nullptr;            // lane-block kernel: tile counters (one per XCD + a departure count), zero between launches
+    void* d_tplan = nullptr;           // plane-quad KIND 4: per-tile staging plans of the current launch (zeroed when allocated)
+    size_t tplan_bytes = 0;
+    uint32_t tplan_epoch = 0;          // ... epoch of the last launch that shared plans (0 is never used: a zeroed plan is never valid)
     float* d_scratch_out = nullptr;    // staging for host outputs
     double* d_batch_m = nullptr;       // batch launches: n x 12 folded matrices
     std::vector<double> h_batch_m;     // ... and their host staging (must outlive the asynchronous upload)

@@ -53,6 +53,8 @@ struct AffineParams {
     int32_t lds_cap;           // block kernel: bytes of LDS the box may take (the tile-queue word follows)
     int32_t binc_hi[5][3];     // block kernel: Q32.32 increments of the steps between a thread's eight voxels (+8 w, +8 h, -8 w, +4 d, -8 h),
     uint32_t binc_lo[5][3];    // [step kind][source axis]
+    void* tplan;               // plane-quad kernel, KIND 4: per-tile staging plans shared by the chunk layers of a launch (nullptr = off)
+    uint32_t tplan_epoch;      // ... and the launch's epoch: a plan granule counts only if it carries this value
 };
 
 
@@ -215,6 +217,8 @@ hipError_t launch_relayout_swap01(const float* src, float* dst, int D, int H, in
 int quad_max_it();
 int quad_config_count();
 void quad_config(int idx, int* th, int* tw, int* nt);
+int quad_tile_plan_granules(int cfg);   // 16-byte granules of one tile's shared staging plan (KIND 4)
+int quad_tile_plan_lds(int cfg);        // LDS bytes a launch that shares plans needs at least
 int quad_blocks_per_cu(int cfg, int interp, int lds_bytes, bool zid = false);
 hipError_t init_quad_kernels();
 hipError_t launch_relayout_zquad(const float* src, float* dst, int D, int H, int W, int P, int Pq, hipStream_t stream);

@@ -47,6 +47,17 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kQuadMaxIt = 5;     // staging instructions per thread and quad: footprints (with row padding) up to 5 * NT vectors
 
+// Per-tile staging plan of KIND 4 (rows 1, 2 of an axis-0-separable map ignore d, so the row-span table, the placement and vrow[] are
+// the same for every chunk layer of a tile).  The plan is the table's LDS image -- tab[0..kTabInts) and the vrow bytes a workgroup of NT
+// threads can stage -- cut into 16-byte granules of three image words and the launch epoch.  The first workgroup of a tile that finds no
+// plan with the current epoch in EVERY granule builds the table as before and publishes it; later layers load it instead.  Nobody waits
+// for anybody: a stale (earlier launch, another matrix), partly written or not yet visible plan only means that the workgroup builds its
+// own.  Producers of one tile write identical bytes (the unused words are zeroed).
+template <int NT> constexpr int quad_plan_granules() { return (kTabInts + NT * kQuadMaxIt / 4 + 2) / 3; }
+// LDS of a sharing launch: the table (kTabBytes), the loaded image (3 words per granule, 16-byte aligned), one vote word per wave
+constexpr int quad_plan_vote_off(int granules) { return kTabBytes + ((12 * granules + 15) & ~15); }
+constexpr int quad_plan_lds_bytes(int granules, int nt) { return quad_plan_vote_off(granules) + 4 * (nt / 64); }
+
 // plain [z][y][P] -> quad layout [z/4][y][Pq]: element (z, y, x) at 4x + (z & 3) of row ((z >> 2), y); positions W .. Wq-1
 // of every row stay zero (the border colour; the staging loads fetch position W of row 0 for every out-of-volume vector)
 __global__ __launch_bounds__(256) void relayout_zquad(const float* __restrict__ src, float* __restrict__ dst,
@@ -286,6 +297,8 @@ template <int KIND, int TH, int TW, int NT>
 __global__ __launch_bounds__(NT, (KIND == 4 && TH * TW == 2 * NT) ? 4 : 1) void affine_march4(const float* __restrict__ srcq, float* __restrict__ out, const AffineParams p)
 {
     static_assert(NT % TW == 0 && TH % (NT / TW) == 0 && NT % 64 == 0 && 64 % TW == 0, "tile/thread mapping");
+    static_assert(NT == 256 || NT == 512, "quad_tile_plan_granules");
+    static_assert(quad_plan_granules<NT>() <= NT && 3 * quad_plan_granules<NT>() <= kTabInts + kVrowCap / 4, "one plan granule per thread");
     constexpr bool CUBIC = KIND == 1 || KIND == 2 || KIND == 4;      // in-plane stencil: 4 x 4 (else 2 x 2)
     constexpr bool ZID = KIND == 3 || KIND == 4;  // integer axis-0 offset: ONE tap plane per output plane (KIND 3: trilinear, the other plane has
                                                   // weight 0; KIND 4: cubic on the z-convolved copy, relayout_zquad_fir)
@@ -326,6 +339,16 @@ __global__ __launch_bounds__(NT, (KIND == 4 && TH * TW == 2 * NT) ? 4 : 1) void 
         march_tile(p, t, th_i, tw_i, chunk);
     }
     const int h0 = th_i * TH, w0 = tw_i * TW;
+    // KIND 4: this tile's shared plan, loaded first so that its L2 round trip overlaps the geometry below; sc1 loads are served by the
+    // XCD's L2, never by this CU's L1 (which may hold the lines of an earlier read)
+    constexpr int PG = quad_plan_granules<NT>();
+    const bool share = KIND == 4 && p.tplan != nullptr;
+    int4 pgran = {0, 0, 0, 0};
+    int4* const plan_g = share ? reinterpret_cast<int4*>(p.tplan) + (int64_t)(th_i * p.nTw + tw_i) * PG : nullptr;
+    if (share && tid < PG) {
+        const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc(plan_g, 0, PG * 16, 0x00020000);
+        pgran = __builtin_bit_cast(int4, __builtin_amdgcn_raw_buffer_load_b128(prsrc, 16 * tid, 0, 16));     // aux 16: sc1
+    }
     const int d_begin = chunk ? chunk * p.dch + p.dshift : 0;
     const int d_end = min((chunk + 1) * p.dch + p.dshift, p.oD);
 
@@ -434,84 +457,125 @@ __global__ __launch_bounds__(NT, (KIND == 4 && TH * TW == 2 * NT) ? 4 : 1) void 
     int nvec;
     {
         int* tab = reinterpret_cast<int*>(lds);   // [0..63] column min -> span start, [64..127] column max -> first vector, [128] total
-        unsigned char* vrow = reinterpret_cast<unsigned char*>(tab + kTabInts);
 #ifdef VT_QUAD_ANALYTIC_SPANS                     // A/B: the float64 polygon clipping of the plain / pair marching kernels
         build_span_table<TH, TW, HALO, 1>(tab, p, p.Ly, by, bx, tid);
 #else
         if (tid < 2 * kRowsMax) tab[tid] = (tid < kRowsMax) ? 0x7fffffff : (int)0x80000000;
+        // KIND 4 with a shared plan: the loaded granules go to their own LDS image beside the table; each wave votes whether all of its
+        // granules carry this launch's epoch, and the workgroup uses the image only if every wave did (the vote shares the barrier
+        // behind the table's initialisation)
+        int* const img = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + kTabBytes);
+        int* const vote = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + quad_plan_vote_off(PG));
+        if (share) {
+            if (tid < PG) { img[3 * tid] = pgran.x; img[3 * tid + 1] = pgran.y; img[3 * tid + 2] = pgran.z; }
+            const bool wave_ok = __all(tid >= PG || (unsigned)pgran.w == p.tplan_epoch);
+            if ((tid & 63) == 0) vote[tid >> 6] = wave_ok ? 1 : 0;
+        }
         __syncthreads();
+        bool hit = false;
+        if (share) {
+            int all = 1;
 #pragma unroll
-        for (int px = 0; px < NPIX; ++px) {
-            // neighbours along the pixel row (TW divides 64: a pixel row never straddles a wave)
-            const int iy_l = __shfl(iy[px], lane_left), iy_r = __shfl(iy[px], lane_right);
-            const bool edge = (kw == 0) || (kw == TW - 1) || (iy_l != iy[px]) || (iy_r != iy[px]);
-            if (edge) {
+            for (int w = 0; w < NT / 64; ++w) all &= vote[w];
+            hit = __builtin_amdgcn_readfirstlane(all) != 0;
+        }
+        if (hit) {
+            tab = img;                            // the same layout: tab[0..kTabInts), then the vrow bytes
+#ifdef VT_EXPERIMENTS
+            stamp[2] = stamp[3] = clock64();      // a hit leaves a placement phase of exactly 0 cycles (tools/setup_phases.py counts them)
+#endif
+        } else {
+            unsigned char* vrow = reinterpret_cast<unsigned char*>(tab + kTabInts);
 #pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    const int row = min(max(iy[px] - HALO + r, 0), kRowsMax - 1);
-                    atomicMin(&tab[row], ix[px] - HALO);
-                    atomicMax(&tab[kRowsMax + row], ix[px] + HALO + 1);
+            for (int px = 0; px < NPIX; ++px) {
+                // neighbours along the pixel row (TW divides 64: a pixel row never straddles a wave)
+                const int iy_l = __shfl(iy[px], lane_left), iy_r = __shfl(iy[px], lane_right);
+                const bool edge = (kw == 0) || (kw == TW - 1) || (iy_l != iy[px]) || (iy_r != iy[px]);
+                if (edge) {
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) {
+                        const int row = min(max(iy[px] - HALO + r, 0), kRowsMax - 1);
+                        atomicMin(&tab[row], ix[px] - HALO);
+                        atomicMax(&tab[kRowsMax + row], ix[px] + HALO + 1);
+                    }
                 }
             }
-        }
-        __syncthreads();
+            __syncthreads();
 #ifdef VT_EXPERIMENTS
-        stamp[2] = clock64();
+            stamp[2] = clock64();
 #endif
-        if (tid < kRowsMax) {
-            const int lane = tid;
-            const int mn = tab[lane], mx = tab[kRowsMax + lane];
-            const bool used = mn <= mx;
-            const int x0 = used ? mn : 0;
-            const int nv = used ? (mx - mn + 1) : 0;
-            int first, pad = 0, total;
-            {
-                const int incl = wave_scan_add(nv);
-                first = incl - nv;
-                total = __builtin_amdgcn_readlane(incl, 63);
+            if (tid < kRowsMax) {
+                const int lane = tid;
+                const int mn = tab[lane], mx = tab[kRowsMax + lane];
+                const bool used = mn <= mx;
+                const int x0 = used ? mn : 0;
+                const int nv = used ? (mx - mn + 1) : 0;
+                int first, pad = 0, total;
+                {
+                    const int incl = wave_scan_add(nv);
+                    first = incl - nv;
+                    total = __builtin_amdgcn_readlane(incl, 63);
+                }
+                if (p.row_s >= 0) {
+                    // Bank-aware row starts (cubic): row r starts at a slot = x0 + r * S (mod 16), i.e. the image behaves like a box
+                    // with row stride S in the 16-slot bank space of ds_read_b128 while only the spans are stored.  The gaps (< 16
+                    // vectors per row) are filled from the zero vector.  S comes from the host's model of the gather's lane groups
+                    // (vt_plan.hip: S = 0 with the service-group lane mapping, quad_row_stride's model otherwise).  If the padded image does
+                    // not fit the slot, the unpadded prefix sum above stays.
+                    // Every row start is pinned to a residue c_r = (x0_r + r * S) mod 16, so the gap in front of row r depends on its
+                    // predecessor alone: gap_r = (c_r - c_{r-1} - n_{r-1}) mod 16 -- the placement is one more prefix sum, not a walk over
+                    // the rows (round 2 walked them with readlane in a scalar loop: ~35 dependent iterations while three waves waited).
+                    // Rows in use are usually contiguous (the footprint is convex), but an in-plane minification beyond the stencil's reach
+                    // leaves unused box rows between them: the predecessor is the last row IN USE before this one (a max-scan of the
+                    // used rows' indices finds it); the rows before the first one carry residue 0 and length 0.
+                    const int S = p.row_s;
+                    const int c_r = (x0 + lane * S) & 15;
+                    const int end_res = (nv > 0) ? ((c_r + nv) & 15) : 0;            // residue of the position right behind this row
+                    const int last_used = wave_scan_max((nv > 0) ? lane : -1);
+                    const int prev_row = wave_shift_up1(last_used, -1);              // last row in use strictly before this one (-1: none)
+                    int prev_end = __shfl(end_res, max(prev_row, 0));
+                    if (lane == 0 || prev_row < 0) prev_end = 0;                     // first row in use: the image starts at position 0
+                    const int gap = (nv > 0) ? ((c_r - prev_end) & 15) : 0;
+                    const int inc2 = wave_scan_add(gap + nv);
+                    const int first_p = inc2 - nv, pad_p = gap;
+                    const int pos = __builtin_amdgcn_readlane(inc2, 63);
+                    if (((pos + 63) & ~63) * 16 <= p.slot_floats * 4 && pos <= NT * kQuadMaxIt) { first = first_p; pad = pad_p; total = pos; }
+                }
+                tab[lane] = x0;
+                tab[kRowsMax + lane] = first;
+                if (lane == 0) tab[2 * kRowsMax] = total;
+                const int last = min(first + nv, kVrowCap);
+                for (int v = max(first - pad, 0); v < min(first, kVrowCap); ++v) vrow[v] = 255;
+                // a row's run of entries: bytes up to the next word, whole words, bytes (runs of different lanes share words only at their ends)
+                int v = first;
+                for (; v < last && (v & 3); ++v) vrow[v] = (unsigned char)lane;
+                const unsigned lane4 = (unsigned)lane * 0x01010101u;
+                for (; v + 4 <= last; v += 4) *reinterpret_cast<unsigned*>(vrow + v) = lane4;
+                for (; v < last; ++v) vrow[v] = (unsigned char)lane;
             }
-            if (p.row_s >= 0) {
-                // Bank-aware row starts (cubic): row r starts at a slot = x0 + r * S (mod 16), i.e. the image behaves like a box
-                // with row stride S in the 16-slot bank space of ds_read_b128 while only the spans are stored.  The gaps (< 16
-                // vectors per row) are filled from the zero vector.  S comes from the host's model of the gather's lane groups
-                // (vt_plan.hip: S = 0 with the service-group lane mapping, quad_row_stride's model otherwise).  If the padded image does
-                // not fit the slot, the unpadded prefix sum above stays.
-                // Every row start is pinned to a residue c_r = (x0_r + r * S) mod 16, so the gap in front of row r depends on its
-                // predecessor alone: gap_r = (c_r - c_{r-1} - n_{r-1}) mod 16 -- the placement is one more prefix sum, not a walk over
-                // the rows (round 2 walked them with readlane in a scalar loop: ~35 dependent iterations while three waves waited).
-                // Rows in use are usually contiguous (the footprint is convex), but an in-plane minification beyond the stencil's reach
-                // leaves unused box rows between them: the predecessor is the last row IN USE before this one (a max-scan of the
-                // used rows' indices finds it); the rows before the first one carry residue 0 and length 0.
-                const int S = p.row_s;
-                const int c_r = (x0 + lane * S) & 15;
-                const int end_res = (nv > 0) ? ((c_r + nv) & 15) : 0;            // residue of the position right behind this row
-                const int last_used = wave_scan_max((nv > 0) ? lane : -1);
-                const int prev_row = wave_shift_up1(last_used, -1);              // last row in use strictly before this one (-1: none)
-                int prev_end = __shfl(end_res, max(prev_row, 0));
-                if (lane == 0 || prev_row < 0) prev_end = 0;                     // first row in use: the image starts at position 0
-                const int gap = (nv > 0) ? ((c_r - prev_end) & 15) : 0;
-                const int inc2 = wave_scan_add(gap + nv);
-                const int first_p = inc2 - nv, pad_p = gap;
-                const int pos = __builtin_amdgcn_readlane(inc2, 63);
-                if (((pos + 63) & ~63) * 16 <= p.slot_floats * 4 && pos <= NT * kQuadMaxIt) { first = first_p; pad = pad_p; total = pos; }
-            }
-            tab[lane] = x0;
-            tab[kRowsMax + lane] = first;
-            if (lane == 0) tab[2 * kRowsMax] = total;
-            const int last = min(first + nv, kVrowCap);
-            for (int v = max(first - pad, 0); v < min(first, kVrowCap); ++v) vrow[v] = 255;
-            // a row's run of entries: bytes up to the next word, whole words, bytes (runs of different lanes share words only at their ends)
-            int v = first;
-            for (; v < last && (v & 3); ++v) vrow[v] = (unsigned char)lane;
-            const unsigned lane4 = (unsigned)lane * 0x01010101u;
-            for (; v + 4 <= last; v += 4) *reinterpret_cast<unsigned*>(vrow + v) = lane4;
-            for (; v < last; ++v) vrow[v] = (unsigned char)lane;
-        }
-        __syncthreads();
-#endif
+            __syncthreads();
 #ifdef VT_EXPERIMENTS
-        stamp[3] = clock64();
+            stamp[3] = clock64();
 #endif
+            if (share && tid < PG) {
+                // publish: words past the table's total and past the vrow bytes in use are zero, so every producer of a tile writes the
+                // same bytes; ordinary 16-byte stores (a reader that sees a granule before it lands builds its own table)
+                const int nvb = min(tab[2 * kRowsMax], NT * kQuadMaxIt);
+                int w[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const int k = 3 * tid + j;
+                    const int b = 4 * (k - kTabInts);         // first vrow byte of the word (k >= kTabInts)
+                    int val = 0;
+                    if (k <= 2 * kRowsMax) val = tab[k];
+                    else if (k >= kTabInts && b < nvb) val = tab[k] & ((b + 4 <= nvb) ? -1 : (int)((1u << (8 * (nvb - b))) - 1u));
+                    w[j] = val;
+                }
+                plan_g[tid] = make_int4(w[0], w[1], w[2], (int)p.tplan_epoch);
+            }
+        }
+#endif
+        const unsigned char* vrow = reinterpret_cast<const unsigned char*>(tab + kTabInts);
         nvec = tab[2 * kRowsMax];
 #pragma unroll
         for (int it = 0; it < kQuadMaxIt; ++it) {
@@ -764,6 +828,8 @@ static const QuadCfg kQuad[] = {
 int quad_max_it() { return kQuadMaxIt; }
 int quad_config_count() { return (int)(sizeof(kQuad) / sizeof(kQuad[0])); }
 void quad_config(int idx, int* th, int* tw, int* nt) { *th = kQuad[idx].th; *tw = kQuad[idx].tw; *nt = kQuad[idx].nt; }
+int quad_tile_plan_granules(int cfg) { return kQuad[cfg].nt == 512 ? quad_plan_granules<512>() : quad_plan_granules<256>(); }
+int quad_tile_plan_lds(int cfg) { return quad_plan_lds_bytes(quad_tile_plan_granules(cfg), kQuad[cfg].nt); }
 
 template <int TH, int TW, int NT>
 static quad_fn pick_quad(int kind)

@@ -377,6 +377,12 @@ bool plan_quad(PlanCtx& c)
         if (v->interp == VT_BSPLINE_SIMPLE || v->interp == VT_FILT_BSPLINE_SIMPLE) p->flags |= (1 << 18);
     }
     const bool zfir_on = (p->flags & (1 << 19)) != 0;
+    // KIND 4: the chunk layers of a tile share one staging plan (vt_kernels_quad.hip); the launch site supplies the buffer and the epoch
+    const bool share_plans = zfir_on && !(c.flags & VT_NO_PLANSHARE);
+    if (share_plans) {
+        p->flags |= (1 << 17);
+        plan->lds_bytes = std::max(plan->lds_bytes, quad_tile_plan_lds(plan->cfg));
+    }
     const bool one_plane = zid || zfir_on;
     const int64_t inplane = (int64_t)p->nTh * p->nTw;
     // chunk depth: every chunk pays one quad step beyond its own planes (history of the first outputs), so chunks are deeper than
@@ -394,7 +400,11 @@ bool plan_quad(PlanCtx& c)
     // Round 5 re-check on the final kernel (tile origin in scalar registers, cheaper set-up), one process per variant, 60 angles, three alternations
     // (profiles/r05_headline_chunk_depth.txt): 512^3 0.2064 ms at 16 planes, 0.1905 at 24, 0.1873 at 32, 0.1869 at 40, 0.1880 at 48, 0.1923 at 64 --
     // 32 planes at every size now (1024^3 filt_bspline: 1.563 ms at 64 planes, 1.527 at 32; four-plane kernel: 1.594)
-    if (zfir_on) target_dch = 32;
+    // With the shared per-tile plan (a chunk layer that finds its tile's plan skips the span atomics and the placement) 24 planes win
+    // [measured, one process per variant, three alternations, profiles/pr_plan_share.txt]: 512^3 sweep 0.1892 / 0.1887 / 0.1892 ms at 16
+    // planes, 0.1833 / 0.1839 / 0.1834 at 24, 0.1867 / 0.1852 / 0.1849 at 32 (unshared at 32: 0.1864 / 0.1860 / 0.1864); 1024^3 1.501 / 1.502 /
+    // 1.544 at 16, 1.496 / 1.497 / 1.552 at 24, 1.509 / 1.511 / 1.562 at 32 (unshared at 32: 1.497 / 1.496 / 1.548)
+    if (zfir_on) target_dch = share_plans ? 24 : 32;
     if (zid) target_dch = 16;             // 512^3, one process per variant (profiles/r03_process_ab.txt): 0.1896 ms at 16, 0.1911 at 20, 0.1922 at 24, 0.1953 at 32
     if (one_plane && v->tune.zid_dch > 0) target_dch = v->tune.zid_dch;
     if (v->tune.dch > 0) target_dch = std::max(4, v->tune.dch);
