@@ -33,3 +33,17 @@ def test_legacy_kernel_families_against_the_oracle():
     probe = subprocess.run([sys.executable, '-c', 'from voltools_amd import _native; print(int(_native.has_legacy_kernels()))'],
                            cwd=ROOT, env=env, stdout=subprocess.PIPE, text=True, timeout=300)
     assert probe.stdout.strip().endswith('1'), probe.stdout
+
+
+def test_legacy_kernel_families_on_lattice_and_face_cases():
+    """The axis-0-separable groups of tests/test_gpu_lattice.py under VT_NO_QUAD / VT_NO_ZPAIR / VT_NO_MARCH on the test build: kinds 5 / 4,
+    4 and 3 held to the integer-lattice and skirt-face cases (the node itself asserts that all three kinds served every case group)."""
+    if not os.path.exists(LEGACY_LIB):
+        pytest.skip('test build not present (python -c "import __graft_entry__ as g; g.build()")')
+    env = dict(os.environ, VT_LIB=LEGACY_LIB)
+    cmd = [sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_gpu_lattice.py') + '::test_axis0_separable_cases_on_the_families_of_the_test_build',
+           '-x', '-q', '-m', 'gpu', '-p', 'no:cacheprovider']
+    res = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    tail = res.stdout[-3000:]
+    assert res.returncode == 0, tail
+    assert '1 passed' in tail and 'failed' not in tail, tail
