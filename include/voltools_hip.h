@@ -95,7 +95,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -189,6 +189,24 @@ int vt_volume_affine_f64(vt_volume_t* vol, const double* m4x4, float* out, int f
  * (launch latency, README.md:74, is paid once); larger ones are queued back to back on the handle's stream.
  * With a host `out` the call returns after the copy back; with VT_OUT_DEVICE it returns after the launch. */
 int vt_volume_affine_batch(vt_volume_t* vol, int n, const float* m4x4s, float* out, int flags);
+
+/* ---- batched sub-volume extraction: n boxes of one shape cut out of the resident volume, each at its own position and
+ * orientation (sub-tomogram extraction, particle re-extraction, local template-matching windows).  Extends the reference's
+ * CPU call site transforms.py:136-150 (scipy's `output_shape` argument of affine_transform) to the GPU and to a batch; the
+ * reference's GPU path has no output shape other than the source's.
+ * m4x4s: n x 16 pull matrices; box i is what vt_volume_affine would write for matrix i if the handle's output shape were
+ * (box_d, box_h, box_w): src = M_i[:3,:3] . (d,h,w) + M_i[:3,3] with (d,h,w) the voxel index inside the box, the handle's
+ * interpolation and boundary contract (VT_EDGE_SCIPY handles included).  out: n consecutive boxes; voxels outside the valid
+ * interval are written as 0 (VT_KEEP_OUTSIDE is ignored).  Box i depends on M_i, the source and the box shape only, bit for
+ * bit -- not on n, the other matrices or its place in the batch.  The handle's own output shape is neither read nor changed.
+ * One launch serves every (matrix, box tile) pair (last_kernel 11); matrices whose tile footprint fits no LDS box gather
+ * from global memory inside the same launch.  VT_FORCE_TILED / VT_FORCE_DIRECT select kernel 11 / the batched direct
+ * kernel (last_kernel 1) whatever the box shape.  Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on
+ * the handle's stream.  Slab handles and handles not yet finalized: VT_EINVAL; non-finite matrix entries: VT_EINVAL. */
+int vt_volume_extract(vt_volume_t* vol, int n, const float* m4x4s,
+                      int box_d, int box_h, int box_w, float* out, int flags);
+int vt_volume_extract_f64(vt_volume_t* vol, int n, const double* m4x4s,
+                          int box_d, int box_h, int box_w, float* out, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

@@ -270,6 +270,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_block_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_rows_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_span_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extract_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -1527,6 +1528,123 @@ int do_affine_batch(vt_volume* v, int n, const double* m4x4s, float* out, int fl
     return 0;
 }
 
+// Which box shapes the batched extraction kernel (kind 11) serves by default; the others take the batched direct kernel.
+// The rule follows from profiles/pr_extract.txt: out of a 1024 x 1024 x 512 source kernel 11 took 0.24 / 1.45 /
+// 4.55 / 10.85 us per trilinear box of 32^3 / 64^3 / 96^3 / 128^3 where the former path took 0.66 / 4.62 / 16.74 / 15.45, and
+// 0.42 / 2.70 / 9.06 / 22.11 against 2.86 / 22.15 / 81.19 / 29.13 for filt_bspline -- no measured shape is better off on the old path.
+// VT_FORCE_TILED / VT_FORCE_DIRECT override the rule.
+bool extract_routes_tiled(int interp, int bd, int bh, int bw)
+{
+    (void)interp; (void)bd; (void)bh; (void)bw;
+    return true;
+}
+
+// n boxes of one shape cut out of the resident volume, one pull matrix each (sub-tomogram extraction): scipy's output_shape
+// (transforms.py:136-150) per matrix, in one launch.  Does not read or change the handle's own output shape.
+int do_extract(vt_volume* v, int n, const double* m4x4s, int bd, int bh, int bw, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
+    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
+    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
+        return fail(VT_EINVAL, "box extraction is available for whole-volume handles only (this one holds a slab window)");
+    int rc = use_device(v->dev);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+
+    const bool cubic = is_cubic(v->interp);
+    const int box[3] = {bd, bh, bw};
+    const size_t n_box = (size_t)bd * bh * bw;
+    const size_t total = n_box * (size_t)n;
+    const bool host_out = !(flags & VT_OUT_DEVICE);
+    const bool tiled = (flags & VT_FORCE_TILED) || (!(flags & VT_FORCE_DIRECT) && extract_routes_tiled(v->interp, bd, bh, bw));
+
+    // the launch's table: ExtractEntry per matrix (kind 11) or 12 doubles per matrix (batched direct kernel)
+    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
+    const size_t per = tiled ? sizeof(ExtractEntry) / sizeof(double) : 12;
+    std::vector<double>& tab = v->h_batch_m;
+    tab.resize((size_t)n * per);
+    int wg_per_cu = 0;
+    const int cfg = extract_pick_tile(cubic, box, &wg_per_cu);
+    int T[3];
+    extract_tile(cfg, &T[0], &T[1], &T[2]);
+    int Lmax[3] = {0, 0, 0};
+    int64_t lds_bytes = 16;
+    for (int i = 0; i < n; ++i) {
+        const double* a = m4x4s + 16 * (size_t)i;
+        double m[12];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
+            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
+        }
+        if (tiled) {
+            ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
+            extract_fill_entry(m, cfg, cubic, v->lds_limit, false, e);
+            if (e->tiled) {
+                Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
+                lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
+            }
+        } else {
+            std::memcpy(tab.data() + per * (size_t)i, m, sizeof(m));
+        }
+    }
+    AffineParams p;
+    std::memset(&p, 0, sizeof(p));
+    TilePlan plan;
+    {
+        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
+        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
+    }
+    p.nTd = (bd + T[0] - 1) / T[0]; p.nTh = (bh + T[1] - 1) / T[1]; p.nTw = (bw + T[2] - 1) / T[2];
+    const int64_t tiles = (int64_t)p.nTd * p.nTh * p.nTw;
+    if (tiled && tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+
+    if (v->batch_m_cap < tab.size()) {
+        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
+        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
+        v->batch_m_cap = tab.size();
+    }
+    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
+                               hipMemcpyHostToDevice, v->stream));
+    float* d_out = out;
+    PinnedScope pin(host_out ? out : nullptr, host_out ? total * sizeof(float) : 0);
+    if (host_out && (rc = host_output_buffer(v, total, &d_out))) return rc;
+
+    int64_t last_grid = 0;
+    if (tiled) {
+        const int per_launch = (int)std::min<int64_t>(n, 0x7fffffffLL / tiles);
+        for (int first = 0; first < n; first += per_launch) {
+            const int cnt = std::min(per_launch, n - first);
+            last_grid = tiles * cnt;
+            VT_HIP(launch_extract(cfg, v->interp, v->d_src, d_out + (size_t)first * n_box,
+                                  v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m) + first, p, last_grid, (int)lds_bytes, v->stream));
+        }
+        v->last_kernel = 11;
+        v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
+        v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
+        v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)last_grid;
+    } else {
+        for (int first = 0; first < n; first += 65535) {
+            const int cnt = std::min(65535, n - first);
+            VT_HIP(launch_affine_direct_batch(v->interp, v->d_src, d_out + (size_t)first * n_box, v->d_batch_m + 12 * (size_t)first,
+                                              cnt, p, v->stream));
+        }
+        v->last_kernel = 1;
+        v->last_tile[0] = v->last_tile[1] = v->last_tile[2] = 0;
+        v->last_lds[0] = v->last_lds[1] = v->last_lds[2] = 0;
+        v->last_lds_bytes = 0; v->last_grid = (int)((n_box + 255) / 256);
+    }
+    if (host_out) {
+        VT_HIP(pin.copy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+        VT_HIP(hipStreamSynchronize(v->stream));
+    }
+    return 0;
+}
+
 // Axis-0 projection: out[h, w] = sum_d affine(m)[d, h, w]  (see vt_kernels_project.hip)
 int do_project(vt_volume* v, const double m4x4[16], float* out, int flags)
 {
@@ -1961,6 +2079,19 @@ int vt_volume_affine_batch(vt_volume_t* v, int n, const float* m4x4s, float* out
     std::vector<double> m((size_t)n * 16);
     for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
     return do_affine_batch(v, n, m.data(), out, flags);
+}
+
+int vt_volume_extract(vt_volume_t* v, int n, const float* m4x4s, int box_d, int box_h, int box_w, float* out, int flags)
+{
+    if (!v || !m4x4s || !out || n <= 0) return fail(VT_EINVAL, "NULL argument or empty batch");
+    std::vector<double> m((size_t)n * 16);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
+    return do_extract(v, n, m.data(), box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_extract_f64(vt_volume_t* v, int n, const double* m4x4s, int box_d, int box_h, int box_w, float* out, int flags)
+{
+    return do_extract(v, n, m4x4s, box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_project(vt_volume_t* v, const float* m4x4, float* out_hw, int flags)

@@ -267,6 +267,25 @@ hipError_t launch_affine_direct(int interp, const float* src, float* out, const 
                                 hipStream_t stream);
 hipError_t init_affine_kernels();   // raises the dynamic-LDS limit of every tiled instantiation
 
+// batched box extraction (vt_kernels_extract.hip, kind 11): one table entry per matrix, read by its workgroups with scalar loads
+struct ExtractEntry {
+    double m[12];              // 3x4 pull matrix, resident-window and edge offsets folded into m[r][3]
+    double neg[3], pos[3];     // tile reach (set_tile_reach) for the launch's tile
+    int32_t inc_hi[3];         // Q32.32 split of m[r][0]
+    uint32_t inc_lo[3];
+    int32_t Lz, Ly, Lx;        // this entry's staged box (floats); Lx is its LDS row stride
+    int32_t tiled;             // 1: stage into LDS; 0: the footprint fits no LDS box, gather from global memory
+    int32_t pad_[2];
+};
+static_assert(sizeof(ExtractEntry) == 192, "table entries are read with 16-byte scalar loads");
+int extract_tile_count();
+void extract_tile(int idx, int* td, int* th, int* tw);
+int extract_pick_tile(bool cubic, const int box[3], int* wg_per_cu);     // a function of (box shape, interpolation) only
+void extract_fill_entry(const double m[12], int cfg, bool cubic, int lds_cap, bool force_direct, ExtractEntry* e);
+hipError_t init_extract_kernels();
+hipError_t launch_extract(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
+                          const AffineParams& p, int64_t grid, int lds_bytes, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

@@ -27,86 +27,6 @@
 
 namespace vt {
 
-// Stage the source box [o, o+L) into LDS with direct-to-LDS loads (no VGPR round trip, every load of the
-// workgroup in flight at once).  The LDS image is lane-linear: 16-byte vector v of the box lands at
-// lds + 16*v.  Vectors outside the volume are fetched from a 16-byte block of zeros instead, which
-// implements the texture unit's border mode without a second code path.
-__device__ __forceinline__ void stage_box(float* lds, const float* __restrict__ src, const float* __restrict__ zeros16,
-                                          const AffineParams& p, const int (&o)[3], int Lz, int Ly, int Lx, int tid)
-{
-    const int nvx = Lx >> 2;
-    const int total = Lz * Ly * nvx;
-    const int step_rows = 256 / nvx, step_cx = 256 - step_rows * nvx;
-    const int step_z = step_rows / Ly, step_y = step_rows - step_z * Ly;
-    int v = tid;
-    int row = v / nvx;
-    int cx = v - row * nvx;
-    int z = row / Ly;
-    int y = row - z * Ly;
-    const int wave_first = __builtin_amdgcn_readfirstlane(tid & ~63);
-    for (int vb = wave_first; vb < total; vb += 256, v += 256) {
-        const int gz = o[0] + z, gy = o[1] + y, gx = o[2] + 4 * cx;
-        const bool inb = (unsigned)gz < (unsigned)p.sD && (unsigned)gy < (unsigned)p.sH && (unsigned)gx < (unsigned)p.sP;
-        const float* g = inb ? src + (((int64_t)gz * p.sH + gy) * p.sP + gx) : zeros16;
-        if (v < total)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                             (__attribute__((address_space(3))) void*)(lds + 4 * vb), 16, 0, 0);
-        cx += step_cx; y += step_y; z += step_z;
-        if (cx >= nvx) { cx -= nvx; y += 1; }
-        if (y >= Ly) { y -= Ly; z += 1; }
-    }
-}
-
-// One output voxel from the staged box.  (iz,iy,ix) = integer tap origin in box coordinates, f* = fractions.
-template <int KIND>
-__device__ __forceinline__ float sample_box(const float* __restrict__ lds, int Lx, int LyLx,
-                                            int iz, int iy, int ix, float fz, float fy, float fx)
-{
-    if constexpr (KIND == 0) {
-        const float* q = lds + (__mul24(iz, LyLx) + __mul24(iy, Lx) + ix);
-        const float a000 = q[0], a001 = q[1];
-        const float a010 = q[Lx], a011 = q[Lx + 1];
-        const float a100 = q[LyLx], a101 = q[LyLx + 1];
-        const float a110 = q[LyLx + Lx], a111 = q[LyLx + Lx + 1];
-        const float x00 = fmaf(fx, a001 - a000, a000);
-        const float x01 = fmaf(fx, a011 - a010, a010);
-        const float x10 = fmaf(fx, a101 - a100, a100);
-        const float x11 = fmaf(fx, a111 - a110, a110);
-        const float y0 = fmaf(fy, x01 - x00, x00);
-        const float y1 = fmaf(fy, x11 - x10, x10);
-        return fmaf(fz, y1 - y0, y0);
-    } else {
-        float wx[4], wy[4], wz[4];
-        cubic_weights<KIND == 2>(fx, wx);
-        cubic_weights<KIND == 2>(fy, wy);
-        cubic_weights<KIND == 2>(fz, wz);
-#ifndef VT_CUBIC_B32
-        const int x1 = ix - 1, par = x1 & 1, e = x1 - par;
-        const unsigned qa = lds_byte_address(lds + (__mul24(iz - 1, LyLx) + __mul24(iy - 1, Lx) + e));
-        const unsigned row_b = 4u * (unsigned)Lx, plane_b = 4u * (unsigned)LyLx;
-        return cubic_gather_b64([&](int c, int bb) { return qa + (unsigned)c * plane_b + (unsigned)bb * row_b; }, par, wx, wy, wz);
-#else
-        const float* q = lds + (__mul24(iz - 1, LyLx) + __mul24(iy - 1, Lx) + (ix - 1));
-        float val = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float accy = 0.f;
-#pragma unroll
-            for (int bb = 0; bb < 4; ++bb) {
-                const float* rowp = q + c * LyLx + bb * Lx;
-                float accx = wx[0] * rowp[0];
-                accx = fmaf(wx[1], rowp[1], accx);
-                accx = fmaf(wx[2], rowp[2], accx);
-                accx = fmaf(wx[3], rowp[3], accx);
-                accy = fmaf(wy[bb], accx, accy);
-            }
-            val = fmaf(wz[c], accy, val);
-        }
-        return val;
-#endif
-    }
-}
-
 template <int KIND /*0 linear, 1 cubic (bspline_weights), 2 cubic (bspline fn)*/, int TD, int TH, int TW>
 __global__ __launch_bounds__(256) void affine_tiled(const float* __restrict__ src, float* __restrict__ out,
                                                      const float* __restrict__ zeros16, const AffineParams p)

@@ -125,3 +125,42 @@ def transform_matrix(scale: Vec3 = None, shear: Vec3 = None, rotation: Vec3 = No
     m = reduce(np.dot, factors, np.identity(4, dtype=dtype))
     m /= m[3, 3]
     return m
+
+
+def box_matrices(positions, rotations=None, box_shape=None, rotation_units: str = 'deg',
+                 rotation_order: str = 'rzxz') -> np.ndarray:
+    """Pull matrices (n, 4, 4), float64, of ``n`` boxes of shape ``box_shape`` cut out of a volume (``StaticVolume.extract``).
+
+    With ``c = (box_shape - 1) / 2`` and ``R_i = rotation_matrix(rotations[i], ...)[:3, :3]`` (identity when ``rotations`` is
+    None): ``M_i[:3, :3] = R_i`` and ``M_i[:3, 3] = positions[i] - R_i . c``, so the centre of box ``i`` samples the source at
+    ``positions[i]``; with no rotation and an integer ``positions[i] - c`` the box is the plain crop starting there.
+    """
+    box = _box_shape(box_shape)
+    pos = np.asarray(positions, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3 or pos.shape[0] == 0:
+        raise ValueError('positions must have shape (n, 3)')
+    n = pos.shape[0]
+    if rotations is not None:
+        rot = np.asarray(rotations, dtype=np.float64)
+        if rot.ndim != 2 or rot.shape[1] != 3 or rot.shape[0] != n:
+            raise ValueError('rotations must have shape (n, 3), one per position')
+    c = (np.asarray(box, dtype=np.float64) - 1.0) / 2.0
+    ms = np.zeros((n, 4, 4), dtype=np.float64)
+    for i in range(n):
+        r3 = np.identity(3, dtype=np.float64) if rotations is None else \
+            rotation_matrix(rot[i], rotation_units, rotation_order, dtype=np.float64)[:3, :3]
+        ms[i, :3, :3] = r3
+        ms[i, :3, 3] = pos[i] - r3 @ c
+        ms[i, 3, 3] = 1.0
+    return ms
+
+
+def _box_shape(box_shape) -> Tuple[int, int, int]:
+    """Three positive ints, or ValueError."""
+    try:
+        box = tuple(box_shape)
+    except TypeError:
+        raise ValueError('box_shape must be three positive ints')
+    if len(box) != 3 or not all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) and b > 0 for b in box):
+        raise ValueError('box_shape must be three positive ints')
+    return tuple(int(b) for b in box)

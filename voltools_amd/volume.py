@@ -6,14 +6,17 @@ data to ``vt_volume_create`` (upload + one-time three-pass prefilter for ``filt_
 available here, as in the reference (``volume.py:14-16``).
 """
 import ctypes
+import time
 from typing import Tuple, Union
 
 import numpy as np
+from scipy.ndimage import affine_transform, spline_filter
 
 from . import _native
-from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple
-from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix,
+from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
+from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices,
                     get_available_devices, switch_to_device)
+from .utils.matrices import _box_shape
 
 Vec3 = Union[Tuple[float, float, float], np.ndarray]
 
@@ -182,6 +185,66 @@ class StaticVolume:
         if profile:
             print(f'{n} transforms finished in {self.timer_stop():.3f}ms')
         return result
+
+    # -- sub-volume extraction (extension: scipy's output_shape, transforms.py:136-150, per matrix and in one launch) ----
+    def extract(self, matrices: np.ndarray, box_shape, profile: bool = False, output=None, *,
+                _flags: int = 0) -> Union[np.ndarray, None]:
+        """``n`` boxes of shape ``box_shape = (bd, bh, bw)`` cut out of the volume, each through its own pull matrix:
+        box ``i`` is what ``affine(matrices[i])`` would return if the output shape were ``box_shape`` --
+        ``src = M_i[:3, :3] . (d, h, w) + M_i[:3, 3]`` with ``(d, h, w)`` the voxel index inside the box.  Voxels that map outside
+        the volume are 0.  Returns a float32 array ``(n, bd, bh, bw)``, or fills ``output`` of that shape (numpy, ``vt.empty`` device
+        array, torch-ROCm tensor) and returns None on a GPU device, like ``affine_batch``.  Box ``i`` depends on ``matrices[i]`` only,
+        bit for bit.  float64 matrices keep their precision; anything else is taken as float32."""
+        box = _box_shape(box_shape)
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] != (4, 4) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        n = ms.shape[0]
+        shape = (n,) + box
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            data = self.data
+            if prefilter:       # what affine_transform(prefilter=True) does first (mode='constant'), once instead of per box
+                data = spline_filter(data, order, output=np.float64, mode='constant')
+            res = np.empty(shape, dtype=self.data.dtype if np.issubdtype(self.data.dtype, np.floating) else np.float64)
+            t_start = time.time()
+            for i in range(n):
+                affine_transform(data, ms[i], output_shape=box, output=res[i], order=order, prefilter=False)
+            if profile:
+                print(f'{n} boxes extracted in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        if ms.dtype == np.float64:
+            rc = self._lib.vt_volume_extract_f64(self._handle, n, ms.ctypes.data, *box, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_extract(self._handle, n, ms.ctypes.data, *box, ptr, flags)
+        _native.check(rc, 'vt_volume_extract')
+        if profile:
+            print(f'{n} boxes extracted in {self.timer_stop():.3f}ms')
+        return result
+
+    def extract_at(self, positions, rotations=None, box_shape=None, rotation_units: str = 'deg',
+                   rotation_order: str = 'rzxz', profile: bool = False, output=None) -> Union[np.ndarray, None]:
+        """``extract`` of boxes centred at ``positions`` (n, 3), each turned by ``rotations[i]`` (n, 3; none: axis-aligned crops):
+        the matrices of ``utils.box_matrices``, in float64."""
+        return self.extract(box_matrices(positions, rotations, box_shape, rotation_units, rotation_order), box_shape,
+                            profile, output)
 
     # -- projection (SURVEY 8(f)3; examples/projections.py:20-26 does transform(...).sum(axis=0)) -------
     def projection(self, transform_m: np.ndarray, profile: bool = False, output=None,
