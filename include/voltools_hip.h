@@ -95,7 +95,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -216,6 +216,31 @@ int vt_volume_extract_f64(vt_volume_t* vol, int n, const double* m4x4s,
  * transform into an internal buffer and sum it.  Outside voxels contribute 0; VT_KEEP_OUTSIDE is ignored. */
 int vt_volume_project(vt_volume_t* vol, const float* m4x4, float* out_hw, int flags);
 int vt_volume_project_f64(vt_volume_t* vol, const double* m4x4, float* out_hw, int flags);
+
+/* ---- a stack of projections per call: a tilt series (the loop of examples/projections.py:20-26 with the rotation about an axis
+ * perpendicular to the projection axis) without materialising any transformed volume.
+ * m4x4s: n x 16 pull matrices; image i, of shape (height, width), holds at [h, w] the sum over d < depth of what vt_volume_affine would
+ * write at (d, h, w) for matrix i if the handle's output shape were (depth, height, width), under the handle's interpolation and boundary
+ * contract (VT_EDGE_SCIPY handles included).  Outside voxels contribute 0; VT_KEEP_OUTSIDE is ignored.  out: n consecutive images.
+ * The handle's own output shape is not read, and is what it was when the call returns.
+ * The fused kernel (last_kernel 12) serves every (matrix, image tile, depth segment) in one launch: the samples of a pixel are added in
+ * float64 in depth order, depth segments are summed in ascending order by a second small launch and rounded to float32 once; matrices
+ * whose tile footprint fits no LDS box gather from global memory inside the same launch.  Image i depends on M_i, the source, (depth,
+ * height, width) and the route only, bit for bit -- not on n, the other matrices or its place in the batch -- and repeated calls give
+ * identical bits.  Its float64 partial sums live in a buffer the handle recycles, never larger than max(depth * height * width * 4 bytes,
+ * one matrix's partials); larger batches are split into several launches inside the call.
+ * VT_FORCE_TILED selects kernel 12 whatever the shape; VT_FORCE_DIRECT runs the path of vt_volume_project once per matrix inside the call
+ * (last_kernel is what that path reports; it sets the handle's output shape to (depth, height, width) for the duration of the call, and
+ * its internal volume and lazily built copies grow and stay as vt_volume_project would leave them for that shape); otherwise the
+ * route follows from (interpolation, depth, height, width) alone
+ * (kernel 12 for trilinear outputs up to 256 and bspline / filt_bspline outputs up to 64 in every dimension, where it was measured
+ * faster than the loop; the loop elsewhere).
+ * Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  Slab handles and handles not yet
+ * finalized: VT_EINVAL; n <= 0, non-positive dims, non-finite matrix entries: VT_EINVAL. */
+int vt_volume_project_batch(vt_volume_t* vol, int n, const float* m4x4s,
+                            int depth, int height, int width, float* out, int flags);
+int vt_volume_project_batch_f64(vt_volume_t* vol, int n, const double* m4x4s,
+                                int depth, int height, int width, float* out, int flags);
 
 /* ---- timing: replaces the cupy event pairs of profile=True (transforms.py:167-169,214-219; volume.py:65-67,80-85)
  * Events are recorded on the handle's stream. vt_timer_stop synchronises and returns milliseconds. */

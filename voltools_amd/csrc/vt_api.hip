@@ -271,6 +271,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_rows_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_span_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extract_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_projbatch_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -1752,6 +1753,141 @@ int do_project(vt_volume* v, const double m4x4[16], float* out, int flags)
     return 0;
 }
 
+// Which (output shape, interpolation) classes vt_volume_project_batch sends to the fused kernel (kind 12) by default; the others loop over
+// do_project inside the call.  A class takes kernel 12 only where profiles/pr_project_batch.txt shows it to be no
+// slower than that loop by more than the round-to-round spread (<= 0.005 ms on every row); ms per projection, loop -> kernel 12:
+//   trilinear     64^3 0.012 -> 0.003, 128^3 0.017 -> 0.009, 256^3 0.040 -> 0.032: kernel 12 up to 256 in every dimension;
+//                 512^3: 0.264 -> 0.285 (61 tilts about axis 1), 0.275 -> 0.259 (about axis 2), 0.267 -> 0.341 (n = 1), 0.499 -> 0.634 (24 random
+//                 rotations): it loses three rows of four, and the rule cannot see the matrices, so the class loops;
+//   filt_bspline  64^3 0.014 -> 0.006: kernel 12 up to 64 in every dimension; 128^3 0.019 -> 0.024, 256^3 0.047 -> 0.149, 512^3 0.273 -> 1.147 /
+//                 0.358 -> 0.941 / 0.276 -> 1.160 / 0.986 -> 2.129: loop.  `bspline` runs the same instantiations on both arms and follows it.
+// Shapes between two measured sizes belong to the larger one's class; bspline_simple / filt_bspline_simple (kernel 12's KIND 2) were not
+// measured and loop.  VT_FORCE_TILED / VT_FORCE_DIRECT override the rule.
+bool project_batch_routes_fused(int interp, int depth, int height, int width)
+{
+    const int longest = std::max(depth, std::max(height, width));
+    if (interp == VT_LINEAR) return longest <= 256;
+    if (interp == VT_BSPLINE || interp == VT_FILT_BSPLINE) return longest <= 64;
+    return false;
+}
+
+// n projections of the resident volume along output axis 0, one pull matrix each (a tilt series), with an output shape of the call's own:
+// image i = sum over d < depth of what vt_volume_affine would write for matrix i at output shape (depth, height, width).
+int do_project_batch(vt_volume* v, int n, const double* m4x4s, int depth, int height, int width, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    if (depth <= 0 || height <= 0 || width <= 0) return fail(VT_EINVAL, "non-positive output dims (%d,%d,%d)", depth, height, width);
+    if ((int64_t)depth * height > 0x7fffffffLL || (int64_t)height * width > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
+    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
+    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
+        return fail(VT_EINVAL, "batched projection is available for whole-volume handles only (this one holds a slab window)");
+    int rc = use_device(v->dev);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+
+    const size_t n2 = (size_t)height * width;
+    const size_t total = n2 * (size_t)n;
+    const bool host_out = !(flags & VT_OUT_DEVICE);
+    const bool fused = (flags & VT_FORCE_TILED) || (!(flags & VT_FORCE_DIRECT) && project_batch_routes_fused(v->interp, depth, height, width));
+
+    float* d_out = out;
+    PinnedScope pin(host_out ? out : nullptr, host_out ? total * sizeof(float) : 0);
+
+    if (!fused) {
+        // the single-matrix path, once per matrix, on the requested output shape (the handle's own shape is put back before the call returns;
+        // calls on a handle are serialised).  Each image goes to its place in the device buffer; a host `out` is copied once at the end.
+        if (host_out && (rc = host_output_buffer(v, total, &d_out))) return rc;
+        struct ShapeScope {
+            vt_volume* v; int d, h, w;
+            ShapeScope(vt_volume* v_, int od, int oh, int ow) : v(v_), d(v_->oD), h(v_->oH), w(v_->oW) { v->oD = od; v->oH = oh; v->oW = ow; }
+            ~ShapeScope() { v->oD = d; v->oH = h; v->oW = w; }
+        } shape(v, depth, height, width);
+        const int lf = (flags & ~(VT_FORCE_DIRECT | VT_FORCE_TILED | VT_KEEP_OUTSIDE)) | VT_OUT_DEVICE;
+        for (int i = 0; i < n; ++i)
+            if ((rc = do_project(v, m4x4s + 16 * (size_t)i, d_out + (size_t)i * n2, lf))) return rc;
+    } else {
+        const bool cubic = is_cubic(v->interp);
+        int cfg = 0, nseg = 1, tps = 1, T[3];
+        project_batch_shape_plan(cubic, depth, height, width, &cfg, &nseg, &tps);
+        extract_tile(cfg, &T[0], &T[1], &T[2]);
+
+        VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
+        const size_t per = sizeof(ExtractEntry) / sizeof(double);
+        std::vector<double>& tab = v->h_batch_m;
+        tab.resize((size_t)n * per);
+        int Lmax[3] = {0, 0, 0};
+        int64_t lds_bytes = 2048;                         // 256 doubles: the lane groups of the small tiles meet in LDS
+        for (int i = 0; i < n; ++i) {
+            const double* a = m4x4s + 16 * (size_t)i;
+            double m[12];
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
+                m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
+            }
+            ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
+            extract_fill_entry(m, cfg, cubic, v->lds_limit, false, e);
+            if (e->tiled) {
+                Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
+                lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
+            }
+        }
+        AffineParams p;
+        std::memset(&p, 0, sizeof(p));
+        TilePlan plan;
+        {
+            const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, depth, height, width, true);
+            plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, output dims, valid interval
+        }
+        p.nTd = nseg; p.dch = tps;
+        p.nTh = (height + T[1] - 1) / T[1]; p.nTw = (width + T[2] - 1) / T[2];
+        const int64_t units = (int64_t)nseg * p.nTh * p.nTw;
+        if (units > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
+
+        // matrices per launch: the grid limit, and partial sums of no more than max(one output volume in float32, one matrix's partials)
+        int64_t per_launch = std::min<int64_t>(n, 0x7fffffffLL / units);
+        if (nseg > 1) {
+            const size_t image_bytes = (size_t)nseg * n2 * sizeof(double);
+            const size_t cap = std::max((size_t)depth * n2 * sizeof(float), image_bytes);
+            per_launch = std::min<int64_t>(per_launch, (int64_t)(cap / image_bytes));
+            const size_t need = image_bytes * (size_t)per_launch;
+            if (v->proj_part_bytes < need) {
+                if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
+                VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), need));
+                v->proj_part_bytes = need;
+            }
+        }
+        if (v->batch_m_cap < tab.size()) {
+            if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
+            VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
+            v->batch_m_cap = tab.size();
+        }
+        VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
+                                   hipMemcpyHostToDevice, v->stream));
+        if (host_out && (rc = host_output_buffer(v, total, &d_out))) return rc;
+
+        int64_t last_grid = 0;
+        for (int first = 0; first < n; first += (int)per_launch) {
+            const int cnt = (int)std::min<int64_t>(per_launch, n - first);
+            last_grid = units * cnt;
+            VT_HIP(launch_project_tiled(cfg, v->interp, v->d_src, d_out + (size_t)first * n2, v->d_proj_part, v->d_zeros,
+                                        reinterpret_cast<const ExtractEntry*>(v->d_batch_m) + first, p, last_grid, (int)lds_bytes, v->stream));
+            if (nseg > 1) VT_HIP(launch_project_reduce(v->d_proj_part, d_out + (size_t)first * n2, nseg, (int64_t)n2, cnt, v->stream));
+        }
+        v->last_kernel = 12;
+        v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
+        v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
+        v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)last_grid;
+    }
+    if (host_out) {
+        VT_HIP(pin.copy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+        VT_HIP(hipStreamSynchronize(v->stream));
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1958,6 +2094,7 @@ int vt_volume_destroy(vt_volume_t* v)
     }
     if (v->d_scratch_out) cached_free(v->dev, v->d_scratch_out, v->scratch_elems * sizeof(float));
     if (v->d_proj_tmp) hipFree(v->d_proj_tmp);
+    if (v->d_proj_part) cached_free(v->dev, v->d_proj_part, v->proj_part_bytes);
     if (v->d_batch_m) hipFree(v->d_batch_m);
     if (v->proj) { vt_volume_destroy(v->proj); v->proj = nullptr; }
     if (v->ev0) recycle_event(v->dev, v->ev0);
@@ -2105,6 +2242,20 @@ int vt_volume_project(vt_volume_t* v, const float* m4x4, float* out_hw, int flag
 int vt_volume_project_f64(vt_volume_t* v, const double* m4x4, float* out_hw, int flags)
 {
     return do_project(v, m4x4, out_hw, flags);
+}
+
+int vt_volume_project_batch(vt_volume_t* v, int n, const float* m4x4s, int depth, int height, int width, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    std::vector<double> m((size_t)n * 16);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
+    return do_project_batch(v, n, m.data(), depth, height, width, out, flags);
+}
+
+int vt_volume_project_batch_f64(vt_volume_t* v, int n, const double* m4x4s, int depth, int height, int width, float* out, int flags)
+{
+    return do_project_batch(v, n, m4x4s, depth, height, width, out, flags);
 }
 
 int vt_timer_start(vt_volume_t* v)

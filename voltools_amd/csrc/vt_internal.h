@@ -127,7 +127,8 @@ struct PackGeom {
 struct TilePlan {
     int kind;            // 1 direct, 2 tiled, 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled with packed footprints,
                          // 7 reserved (vt_volume_info: fused projection), 8 marching on plane quads, 9 lane-block tiles (cfg = row-stride index),
-                         // 10 source rows along w (maps that leave axis 2 alone)
+                         // 10 source rows along w (maps that leave axis 2 alone); vt_volume_info also reports 11 (batched box extraction) and
+                         // 12 (batched projection), which are planned by their own entry points
     int cfg;             // index into the tile table
     int td, th, tw;
     int lds_bytes;
@@ -285,6 +286,14 @@ void extract_fill_entry(const double m[12], int cfg, bool cubic, int lds_cap, bo
 hipError_t init_extract_kernels();
 hipError_t launch_extract(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
                           const AffineParams& p, int64_t grid, int lds_bytes, hipStream_t stream);
+
+// a stack of axis-0 projections (vt_kernels_projbatch.hip, kind 12): extract_tiled's tiles and table entries, the samples of a pixel
+// summed in float64 along the output depth instead of stored.  AffineParams: nTd = depth segments per image, dch = depth tiles per segment.
+void project_batch_shape_plan(bool cubic, int depth, int height, int width, int* cfg, int* nseg, int* tiles_per_seg);   // (shape, interpolation) only
+hipError_t init_projbatch_kernels();
+hipError_t launch_project_tiled(int cfg, int interp, const float* src, float* out, double* part, const float* zeros16,
+                                const ExtractEntry* d_tab, const AffineParams& p, int64_t grid, int lds_bytes, hipStream_t stream);
+hipError_t launch_project_reduce(const double* part, float* out, int nseg, int64_t plane, int images, hipStream_t stream);
 
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).

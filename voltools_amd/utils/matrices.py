@@ -155,6 +155,27 @@ def box_matrices(positions, rotations=None, box_shape=None, rotation_units: str 
     return ms
 
 
+def tilt_matrices(angles, tilt_axis: int = 1, shape=None, rotation_units: str = 'deg', center: Vec3 = None) -> np.ndarray:
+    """Pull matrices (n, 4, 4) of a tilt series of a volume of shape ``shape`` (``StaticVolume.tilt_series``): matrix ``i`` is
+    ``transform_matrix(rotation=r, rotation_order='sxyz', center=center)`` with ``r`` zero except ``r[tilt_axis] = angles[i]``,
+    i.e. a turn about array axis ``tilt_axis`` (1 or 2: perpendicular to the projection axis, 0: in the image plane).
+    ``center`` defaults to ``(shape - 1) / 2`` in float32, as in ``StaticVolume.project``.
+    """
+    if isinstance(tilt_axis, bool) or not isinstance(tilt_axis, (int, np.integer)) or not 0 <= tilt_axis <= 2:
+        raise ValueError('tilt_axis must be 0, 1 or 2')
+    a = np.asarray(angles, dtype=np.float64)
+    if a.ndim != 1 or a.shape[0] == 0:
+        raise ValueError('angles must be a non-empty sequence')
+    if center is None:
+        center = np.divide(np.subtract(_box_shape(shape), 1), 2, dtype=np.float32)
+    ms = []
+    for angle in a:
+        r = [0.0, 0.0, 0.0]
+        r[int(tilt_axis)] = float(angle)
+        ms.append(transform_matrix(rotation=tuple(r), rotation_units=rotation_units, rotation_order='sxyz', center=center))
+    return np.stack(ms)
+
+
 def _box_shape(box_shape) -> Tuple[int, int, int]:
     """Three positive ints, or ValueError."""
     try:

@@ -14,7 +14,7 @@ from scipy.ndimage import affine_transform, spline_filter
 
 from . import _native
 from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
-from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices,
+from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, tilt_matrices,
                     get_available_devices, switch_to_device)
 from .utils.matrices import _box_shape
 
@@ -296,6 +296,67 @@ class StaticVolume:
         m = transform_matrix(_triple(scale), _triple(shear), rotation, rotation_units, rotation_order,
                              translation, center)
         return self.projection(m, profile, output)
+
+    # -- a stack of projections per call (extension: the loop of examples/projections.py:20-26 for any rotation axis) ----
+    def projection_batch(self, matrices: np.ndarray, output_shape=None, profile: bool = False, output=None, *,
+                         _flags: int = 0) -> Union[np.ndarray, None]:
+        """``n`` projections in one call: image ``i`` is ``affine(matrices[i])`` at output shape ``output_shape = (depth, H, W)``
+        (default: the volume's shape) summed over axis 0, without materialising any transformed volume.  Returns a float32 array
+        ``(n, H, W)``, or fills ``output`` of that shape (numpy, ``vt.empty`` device array, torch-ROCm tensor) and returns None on a GPU
+        device, like ``extract``.  Image ``i`` depends on ``matrices[i]`` only, bit for bit.  float64 matrices keep their precision;
+        anything else is taken as float32."""
+        oshape = tuple(self.shape) if output_shape is None else _box_shape(output_shape)
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] != (4, 4) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        n = ms.shape[0]
+        shape = (n,) + oshape[1:]
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            data = self.data
+            if prefilter:       # what affine_transform(prefilter=True) does first (mode='constant'), once instead of per matrix
+                data = spline_filter(data, order, output=np.float64, mode='constant')
+            res = np.empty(shape, dtype=np.float32)
+            vol = np.empty(oshape, dtype=self.data.dtype if np.issubdtype(self.data.dtype, np.floating) else np.float64)
+            t_start = time.time()
+            for i in range(n):
+                affine_transform(data, ms[i], output_shape=oshape, output=vol, order=order, prefilter=False)
+                res[i] = vol.sum(axis=0, dtype=np.float64)
+            if profile:
+                print(f'{n} projections finished in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        if ms.dtype == np.float64:
+            rc = self._lib.vt_volume_project_batch_f64(self._handle, n, ms.ctypes.data, *oshape, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_project_batch(self._handle, n, ms.ctypes.data, *oshape, ptr, flags)
+        _native.check(rc, 'vt_volume_project_batch')
+        if profile:
+            print(f'{n} projections finished in {self.timer_stop():.3f}ms')
+        return result
+
+    def tilt_series(self, angles, tilt_axis: int = 1, rotation_units: str = 'deg', center: Vec3 = None, output_shape=None,
+                    profile: bool = False, output=None) -> Union[np.ndarray, None]:
+        """``projection_batch`` of the volume turned about array axis ``tilt_axis`` by each of ``angles``: the matrices of
+        ``utils.tilt_matrices``.  ``tilt_series([a], k)[0]`` is the image of ``project(rotation=r, rotation_order='sxyz')`` with
+        ``r[k] = a``."""
+        return self.projection_batch(tilt_matrices(angles, tilt_axis, self.shape, rotation_units, center), output_shape, profile, output)
 
     def translate(self, translation: Vec3, profile: bool = False, output=None):
         return self.affine(translation_matrix(translation), profile, output)
