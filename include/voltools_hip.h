@@ -95,7 +95,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -207,6 +207,29 @@ int vt_volume_extract(vt_volume_t* vol, int n, const float* m4x4s,
                       int box_d, int box_h, int box_w, float* out, int flags);
 int vt_volume_extract_f64(vt_volume_t* vol, int n, const double* m4x4s,
                           int box_d, int box_h, int box_w, float* out, int flags);
+
+/* ---- weighted sum of n extracted boxes (sub-tomogram averaging; symmetrisation with the whole volume as the box) without writing them.
+ * out: ONE box of box_d * box_h * box_w float32 (host, or device with VT_OUT_DEVICE):
+ *     out[d, h, w] = float32(sum_i weights[i] * B_i[d, h, w])
+ * with B_i the float32 box vt_volume_extract writes for matrix i (the handle's interpolation and boundary contract, VT_EDGE_SCIPY handles
+ * included; voxels that map outside are 0).  weights: n float64, or NULL for all 1.  Each sample is widened to float64, multiplied by its
+ * weight (rounded) and added (rounded) to a float64 accumulator, in ascending i within a segment of consecutive matrices; the segments'
+ * sums are added in ascending order and the result is rounded to float32 once.  A voxel no box reaches is +0.
+ * The fused kernel (last_kernel 13) gives one workgroup a box tile and a segment and loops over the segment's matrices; last_grid = box
+ * tiles x segments, last_tile / last_lds_dims / last_lds_bytes as for vt_volume_extract.  The segmentation follows from (n, box shape,
+ * interpolation) alone and the tile is vt_volume_extract's, so the result is a fixed expression of (matrices in their order, weights,
+ * source, box shape, interpolation, route): repeated calls, host and device output and whatever the handle did before give identical bits,
+ * and for n = 1 with weight 1 the result is vt_volume_extract's box bit for bit (up to the sign of a zero) on its default and
+ * VT_FORCE_TILED routes.  Matrices whose tile footprint fits no LDS box gather from global memory inside the same launch; VT_FORCE_DIRECT
+ * makes every matrix do so; VT_FORCE_TILED selects the same kernel as the default; VT_KEEP_OUTSIDE is ignored.  Device memory beyond the
+ * source: n x 200 bytes of tables and, with more than one segment, float64 partials of segments x box voxels (tiles x segments < 2048:
+ * under 64 MiB), in a buffer the handle recycles.  The handle's own output shape is neither read nor changed.
+ * Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  Slab handles and handles not yet
+ * finalized: VT_EINVAL; n <= 0, non-positive box dims, non-finite matrix entries or weights: VT_EINVAL. */
+int vt_volume_extract_sum(vt_volume_t* vol, int n, const float* m4x4s, const double* weights /* n, or NULL = all 1 */,
+                          int box_d, int box_h, int box_w, float* out, int flags);
+int vt_volume_extract_sum_f64(vt_volume_t* vol, int n, const double* m4x4s, const double* weights /* n, or NULL = all 1 */,
+                              int box_d, int box_h, int box_w, float* out, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

@@ -32,6 +32,7 @@ SYMBOLS = [
     'vt_timer_start', 'vt_timer_stop', 'vt_prefilter_inplace', 'vt_affine_oneshot',
     'vt_last_error', 'vt_version', 'vt_has_legacy_kernels', 'vt_volume_release_copies', 'vt_volume_set_max_resident',
     'vt_volume_extract', 'vt_volume_extract_f64', 'vt_volume_project_batch', 'vt_volume_project_batch_f64',
+    'vt_volume_extract_sum', 'vt_volume_extract_sum_f64',
 ]
 
 
@@ -115,6 +116,8 @@ def load():
     L.vt_volume_affine_batch.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int]
     L.vt_volume_extract.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_extract_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_extract_sum.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_extract_sum_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int]

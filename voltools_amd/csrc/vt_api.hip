@@ -272,6 +272,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_span_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extract_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_projbatch_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractsum_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -1888,6 +1889,102 @@ int do_project_batch(vt_volume* v, int n, const double* m4x4s, int depth, int he
     return 0;
 }
 
+// One box: the weighted sum of the n boxes do_extract would write (sub-tomogram averaging; symmetrisation with the volume as the box), in
+// one launch of kernel 13 (vt_kernels_extractsum.hip) and, when the matrices are split into segments, a small reduction.  The boxes are
+// never written.  Does not read or change the handle's own output shape.
+int do_extract_sum(vt_volume* v, int n, const double* m4x4s, const double* weights, int bd, int bh, int bw, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
+    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
+    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
+        return fail(VT_EINVAL, "box summation is available for whole-volume handles only (this one holds a slab window)");
+    int rc = use_device(v->dev);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    if (weights)
+        for (int i = 0; i < n; ++i)
+            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %d is not finite", i);
+
+    const bool cubic = is_cubic(v->interp);
+    const int box[3] = {bd, bh, bw};
+    const size_t n_box = (size_t)bd * bh * bw;
+    const bool host_out = !(flags & VT_OUT_DEVICE);
+    const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
+    int cfg = 0, nseg = 1, per_seg = n, T[3];
+    extract_sum_shape_plan(cubic, box, n, &cfg, &nseg, &per_seg);
+    extract_tile(cfg, &T[0], &T[1], &T[2]);
+
+    // the launch's tables: one ExtractEntry per matrix, then the n weights
+    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
+    const size_t per = sizeof(ExtractEntry) / sizeof(double);
+    std::vector<double>& tab = v->h_batch_m;
+    tab.resize((size_t)n * (per + 1));
+    int Lmax[3] = {0, 0, 0};
+    int64_t lds_bytes = 16;
+    for (int i = 0; i < n; ++i) {
+        const double* a = m4x4s + 16 * (size_t)i;
+        double m[12];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
+            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
+        }
+        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
+        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, e);
+        if (e->tiled) {
+            Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
+            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
+        }
+        tab[per * (size_t)n + (size_t)i] = weights ? weights[i] : 1.0;
+    }
+    AffineParams p;
+    std::memset(&p, 0, sizeof(p));
+    TilePlan plan;
+    {
+        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
+        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
+    }
+    p.nTd = (bd + T[0] - 1) / T[0]; p.nTh = (bh + T[1] - 1) / T[1]; p.nTw = (bw + T[2] - 1) / T[2];
+    const int64_t grid = (int64_t)p.nTd * p.nTh * p.nTw * nseg;
+    if (grid > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+
+    if (nseg > 1) {
+        const size_t need = (size_t)nseg * n_box * sizeof(double);       // tiles x nseg < 2048: under 64 MiB
+        if (v->proj_part_bytes < need) {
+            if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
+            VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), need));
+            v->proj_part_bytes = need;
+        }
+    }
+    if (v->batch_m_cap < tab.size()) {
+        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
+        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
+        v->batch_m_cap = tab.size();
+    }
+    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
+                               hipMemcpyHostToDevice, v->stream));
+    float* d_out = out;
+    PinnedScope pin(host_out ? out : nullptr, host_out ? n_box * sizeof(float) : 0);
+    if (host_out && (rc = host_output_buffer(v, n_box, &d_out))) return rc;
+
+    VT_HIP(launch_extract_sum(cfg, v->interp, v->d_src, d_out, v->d_proj_part, v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m),
+                              v->d_batch_m + per * (size_t)n, n, per_seg, nseg, p, (int)lds_bytes, v->stream));
+    if (nseg > 1) VT_HIP(launch_project_reduce(v->d_proj_part, d_out, nseg, (int64_t)n_box, 1, v->stream));
+    v->last_kernel = 13;
+    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
+    v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
+    v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)grid;
+    if (host_out) {
+        VT_HIP(pin.copy(out, d_out, n_box * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+        VT_HIP(hipStreamSynchronize(v->stream));
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2229,6 +2326,22 @@ int vt_volume_extract(vt_volume_t* v, int n, const float* m4x4s, int box_d, int 
 int vt_volume_extract_f64(vt_volume_t* v, int n, const double* m4x4s, int box_d, int box_h, int box_w, float* out, int flags)
 {
     return do_extract(v, n, m4x4s, box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_extract_sum(vt_volume_t* v, int n, const float* m4x4s, const double* weights, int box_d, int box_h, int box_w, float* out,
+                          int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    std::vector<double> m((size_t)n * 16);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
+    return do_extract_sum(v, n, m.data(), weights, box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_extract_sum_f64(vt_volume_t* v, int n, const double* m4x4s, const double* weights, int box_d, int box_h, int box_w, float* out,
+                              int flags)
+{
+    return do_extract_sum(v, n, m4x4s, weights, box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_project(vt_volume_t* v, const float* m4x4, float* out_hw, int flags)

@@ -139,7 +139,8 @@ struct vt_volume {
     size_t batch_m_cap = 0;
     float* d_proj_tmp = nullptr;       // projection of general matrices: the transformed volume before the sum
     size_t proj_tmp_elems = 0;
-    double* d_proj_part = nullptr;     // batched projection (kind 12): float64 partial sums [matrix][segment][h][w] of one launch (recycled like d_scratch_out)
+    double* d_proj_part = nullptr;     // batched projection (kind 12): float64 partial sums [matrix][segment][h][w] of one launch (recycled like d_scratch_out);
+                                       // also the partials [segment][d][h][w] of a weighted box sum (kind 13)
     size_t proj_part_bytes = 0;
     vt_volume* proj = nullptr;         // projection helper: 3 x H x W volume [S, S, S] sharing this handle's stream
     bool proj_sum_valid = false;       // the helper holds the weighted plane sum of (proj_sum_m3, proj_sum_oD, proj_sum_oplane0)

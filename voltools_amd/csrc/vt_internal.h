@@ -127,8 +127,8 @@ struct PackGeom {
 struct TilePlan {
     int kind;            // 1 direct, 2 tiled, 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled with packed footprints,
                          // 7 reserved (vt_volume_info: fused projection), 8 marching on plane quads, 9 lane-block tiles (cfg = row-stride index),
-                         // 10 source rows along w (maps that leave axis 2 alone); vt_volume_info also reports 11 (batched box extraction) and
-                         // 12 (batched projection), which are planned by their own entry points
+                         // 10 source rows along w (maps that leave axis 2 alone); vt_volume_info also reports 11 (batched box extraction),
+                         // 12 (batched projection) and 13 (weighted sum of boxes), which are planned by their own entry points
     int cfg;             // index into the tile table
     int td, th, tw;
     int lds_bytes;
@@ -294,6 +294,15 @@ hipError_t init_projbatch_kernels();
 hipError_t launch_project_tiled(int cfg, int interp, const float* src, float* out, double* part, const float* zeros16,
                                 const ExtractEntry* d_tab, const AffineParams& p, int64_t grid, int lds_bytes, hipStream_t stream);
 hipError_t launch_project_reduce(const double* part, float* out, int nseg, int64_t plane, int images, hipStream_t stream);
+
+// weighted sum of n extracted boxes (vt_kernels_extractsum.hip, kind 13): extract_tiled's tiles and table entries plus a table of n float64
+// weights; a workgroup owns one box tile and one segment of consecutive matrices.  AffineParams: nTd / nTh / nTw = box tiles.  With nseg > 1
+// the partials [segment][d][h][w] go through launch_project_reduce(part, out, nseg, box voxels, 1, stream).
+void extract_sum_shape_plan(bool cubic, const int box[3], int n, int* cfg, int* nseg, int* per_seg);   // (n, box shape, interpolation) only
+hipError_t init_extractsum_kernels();
+hipError_t launch_extract_sum(int cfg, int interp, const float* src, float* out, double* part, const float* zeros16,
+                              const ExtractEntry* d_tab, const double* d_wts, int n, int per_seg, int nseg, const AffineParams& p,
+                              int lds_bytes, hipStream_t stream);
 
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).

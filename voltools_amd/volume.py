@@ -246,6 +246,78 @@ class StaticVolume:
         return self.extract(box_matrices(positions, rotations, box_shape, rotation_units, rotation_order), box_shape,
                             profile, output)
 
+    # -- weighted sum of extracted boxes (extension: sub-tomogram averaging, symmetrisation; no reference counterpart) ----
+    def extract_sum(self, matrices: np.ndarray, box_shape, weights=None, profile: bool = False, output=None, *,
+                    _flags: int = 0) -> Union[np.ndarray, None]:
+        """``float32(sum_i weights[i] * extract(matrices, box_shape)[i])`` without writing the boxes: one box of shape ``box_shape``.
+        Every sample is widened to float64, multiplied by its float64 weight and added in float64, in the order of ``matrices``; the sum is
+        rounded to float32 once.  ``weights``: shape ``(n,)``, converted to float64; None = ones.  Returns a float32 array ``(bd, bh, bw)``,
+        or fills ``output`` of that shape (numpy, ``vt.empty`` device array, torch-ROCm tensor) and returns None on a GPU device, like
+        ``extract``.  Repeated calls give identical bits.  float64 matrices keep their precision; anything else is taken as float32."""
+        box = _box_shape(box_shape)
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] != (4, 4) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        n = ms.shape[0]
+        w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f'weights must have shape ({n},)')
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        if output is not None and tuple(getattr(output, 'shape', ())) != box:
+            raise ValueError(f'output must have shape {box}')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            data = self.data
+            if prefilter:       # what affine_transform(prefilter=True) does first (mode='constant'), once instead of per box
+                data = spline_filter(data, order, output=np.float64, mode='constant')
+            one = np.empty(box, dtype=self.data.dtype if np.issubdtype(self.data.dtype, np.floating) else np.float64)
+            acc = np.zeros(box, dtype=np.float64)
+            t_start = time.time()
+            for i in range(n):
+                affine_transform(data, ms[i], output_shape=box, output=one, order=order, prefilter=False)
+                acc += w[i] * one.astype(np.float64)
+            res = acc.astype(np.float32)
+            if profile:
+                print(f'{n} boxes summed in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = _native.host_result(box, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, box, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        if ms.dtype == np.float64:
+            rc = self._lib.vt_volume_extract_sum_f64(self._handle, n, ms.ctypes.data, w.ctypes.data, *box, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_extract_sum(self._handle, n, ms.ctypes.data, w.ctypes.data, *box, ptr, flags)
+        _native.check(rc, 'vt_volume_extract_sum')
+        if profile:
+            print(f'{n} boxes summed in {self.timer_stop():.3f}ms')
+        return result
+
+    def average_at(self, positions, rotations=None, box_shape=None, weights=None, rotation_units: str = 'deg',
+                   rotation_order: str = 'rzxz', profile: bool = False, output=None) -> Union[np.ndarray, None]:
+        """Weighted average of the boxes ``extract_at`` would cut: ``extract_sum`` of ``utils.box_matrices(...)`` with ``weights``
+        (None: ones) divided by their sum on the host in float64."""
+        ms = box_matrices(positions, rotations, box_shape, rotation_units, rotation_order)
+        w = np.ones(ms.shape[0], dtype=np.float64) if weights is None else np.asarray(weights, dtype=np.float64)
+        if w.shape != (ms.shape[0],):
+            raise ValueError(f'weights must have shape ({ms.shape[0]},)')
+        total = w.sum()
+        if not np.isfinite(w).all() or total == 0:
+            raise ValueError('weights must be finite and must not sum to 0')
+        return self.extract_sum(ms, box_shape, w / total, profile, output)
+
     # -- projection (SURVEY 8(f)3; examples/projections.py:20-26 does transform(...).sum(axis=0)) -------
     def projection(self, transform_m: np.ndarray, profile: bool = False, output=None,
                    _flags: int = 0) -> Union[np.ndarray, None]:
