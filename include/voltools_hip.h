@@ -95,7 +95,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -230,6 +230,29 @@ int vt_volume_extract_sum(vt_volume_t* vol, int n, const float* m4x4s, const dou
                           int box_d, int box_h, int box_w, float* out, int flags);
 int vt_volume_extract_sum_f64(vt_volume_t* vol, int n, const double* m4x4s, const double* weights /* n, or NULL = all 1 */,
                               int box_d, int box_h, int box_w, float* out, int flags);
+
+/* ---- per-box template scores: three float64 sums over each of n boxes, without writing the boxes ----
+ * out[i] = (sum_v mask[v] * B_i[v], sum_v mask[v] * B_i[v]^2, sum_v tmpl[v] * B_i[v]), where B_i is the float32 box vt_volume_extract
+ * writes for matrix i (the handle's interpolation and boundary contract, VT_EDGE_SCIPY handles included; voxels that map outside are 0)
+ * and v runs over all box voxels: what scoring n candidate (position, orientation) pairs against one template needs.  tmpl, mask: host
+ * float32 arrays of the box shape in C order, uploaded on every call into a buffer the handle recycles; mask NULL = all 1.
+ * out: n x 3 float64 (host, or device with VT_OUT_DEVICE).  Each sample is widened to float64; mask * b and tmpl * b are exact,
+ * (mask * b) * b is rounded once, every addition is rounded.  A thread of the fused kernel (last_kernel 14) adds its own voxels in a fixed
+ * order, a workgroup reduces its 256 partial triples by a tree of fixed shape, and the tiles of a box are added in ascending tile index by
+ * a second small kernel; there are no atomics.  One workgroup serves one (matrix, box tile) pair with vt_volume_extract's tile, stepping
+ * and routing, so the samples are vt_volume_extract's bit for bit and out[i] is a fixed expression of (M_i, tmpl, mask, source, box
+ * shape, interpolation, route): it does not depend on n, on the other matrices or on its place in the batch, and repeated calls, host or
+ * device output and whatever the handle did before leave the bits unchanged.  Matrices whose tile footprint fits no LDS box gather from
+ * global memory inside the same launch; VT_FORCE_DIRECT forces every entry onto that gather, VT_FORCE_TILED is the default route.
+ * The partials (n x box tiles x 3 float64) live in a buffer the handle recycles; a call whose partials would exceed 64 MiB is split
+ * into several launches.  last_tile / last_lds_dims / last_lds_bytes as for vt_volume_extract, last_grid = box tiles x matrices of the
+ * last launch.  The handle's own output shape is neither read nor changed; VT_KEEP_OUTSIDE is ignored.
+ * Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  Slab handles and handles not yet
+ * finalized: VT_EINVAL; n <= 0, NULL tmpl or out, non-positive box dims, non-finite matrix, template or mask entries: VT_EINVAL. */
+int vt_volume_extract_dot(vt_volume_t* vol, int n, const float* m4x4s, const float* tmpl, const float* mask /* or NULL = all 1 */,
+                          int box_d, int box_h, int box_w, double* out /* n x 3 */, int flags);
+int vt_volume_extract_dot_f64(vt_volume_t* vol, int n, const double* m4x4s, const float* tmpl, const float* mask /* or NULL = all 1 */,
+                              int box_d, int box_h, int box_w, double* out /* n x 3 */, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

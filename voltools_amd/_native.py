@@ -32,7 +32,7 @@ SYMBOLS = [
     'vt_timer_start', 'vt_timer_stop', 'vt_prefilter_inplace', 'vt_affine_oneshot',
     'vt_last_error', 'vt_version', 'vt_has_legacy_kernels', 'vt_volume_release_copies', 'vt_volume_set_max_resident',
     'vt_volume_extract', 'vt_volume_extract_f64', 'vt_volume_project_batch', 'vt_volume_project_batch_f64',
-    'vt_volume_extract_sum', 'vt_volume_extract_sum_f64',
+    'vt_volume_extract_sum', 'vt_volume_extract_sum_f64', 'vt_volume_extract_dot', 'vt_volume_extract_dot_f64',
 ]
 
 
@@ -118,6 +118,8 @@ def load():
     L.vt_volume_extract_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_extract_sum.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_extract_sum_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_extract_dot.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_extract_dot_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int]
@@ -362,24 +364,29 @@ def host_result(shape, device: int = 0) -> np.ndarray:
     return _host_pool.take(tuple(int(s) for s in shape), device)
 
 
-def resolve_output(output, shape, device: int) -> Tuple[Optional[int], bool, Optional[np.ndarray]]:
+def resolve_output(output, shape, device: int, dtype=np.float32) -> Tuple[Optional[int], bool, Optional[np.ndarray]]:
     """Classify an ``output=`` argument -> (pointer, is_device, numpy array to fill or None).
 
     Accepted: ``DeviceArray``; anything exposing ``__cuda_array_interface__`` (torch-ROCm tensors,
-    cupy-on-ROCm arrays) -- float32, C-contiguous, right shape; or a numpy float32 array (host).
+    cupy-on-ROCm arrays) -- ``dtype`` (float32 unless the entry point writes float64), C-contiguous, right shape; or a numpy
+    array of that dtype (host).
     """
     shape = tuple(int(s) for s in shape)
+    dt = np.dtype(dtype)
     if isinstance(output, np.ndarray):
-        if output.dtype != np.float32 or not output.flags.c_contiguous or output.shape != shape:
-            raise ValueError('output must be a C-contiguous float32 array of the volume shape')
+        if output.dtype != dt or not output.flags.c_contiguous or output.shape != shape:
+            raise ValueError(f'output must be a C-contiguous {dt.name} array of shape {shape}' if dt != np.float32
+                             else 'output must be a C-contiguous float32 array of the volume shape')
         return output.ctypes.data, False, output
     iface = getattr(output, '__cuda_array_interface__', None)
     if iface is None:
         raise TypeError(f'unsupported output type {type(output)}')
-    if tuple(iface['shape']) != shape or iface['typestr'] not in ('<f4', '=f4', 'f4'):
-        raise ValueError('device output must be float32 of the volume shape')
+    code = f'f{dt.itemsize}'
+    if tuple(iface['shape']) != shape or iface['typestr'] not in ('<' + code, '=' + code, code):
+        raise ValueError(f'device output must be {dt.name} of shape {shape}' if dt != np.float32
+                         else 'device output must be float32 of the volume shape')
     if iface.get('strides') is not None:
-        expect = tuple(int(np.prod(shape[i + 1:])) * 4 for i in range(len(shape)))
+        expect = tuple(int(np.prod(shape[i + 1:])) * dt.itemsize for i in range(len(shape)))
         if tuple(iface['strides']) != expect:
             raise ValueError('device output must be C-contiguous')
     dev_attr = getattr(output, 'device', None)

@@ -53,6 +53,7 @@ struct Tuning {
     int span = 1;                  // VT_SPAN=0: trilinear general matrices on round 1's packed-footprint kernel (vt_kernels_packed.hip) instead of round 5's (A/B)
     int span_pipe = 0;             // VT_SPAN_PIPE: 1 / 0 = trilinear general matrices on the software-pipelined / the single-buffer form of the packed-span kernel, -1 = the planner's cost model
     int block_th = 8;              // VT_BLOCK_TH: tile height of the lane-block kernel: 8 (8 x 8 x 16 tiles, four workgroups per CU; boxes beyond 40 KiB fall back to 16) or 16 (8 x 16 x 16, two per CU)
+    int64_t dot_part_cap = 64ll << 20;   // VT_DOT_PART_CAP: bytes of float64 partials one launch of the per-box score kernel (kind 14) may use (tests of the split)
     void read()
     {
         auto num = [](const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; };
@@ -105,6 +106,7 @@ struct Tuning {
         { const char* e = std::getenv("VT_MAX_RESIDENT_GB"); max_resident_gb = e ? std::atof(e) : 0.0; }
         block_min = std::max(1, num("VT_BLOCK_MIN", 240));
         block_no_trim = std::getenv("VT_BLOCK_NO_TRIM") != nullptr;
+        { const char* e = std::getenv("VT_DOT_PART_CAP"); if (e && std::atoll(e) > 0) dot_part_cap = std::min<int64_t>(std::atoll(e), 64ll << 20); }
     }
 };
 
@@ -140,7 +142,7 @@ struct vt_volume {
     float* d_proj_tmp = nullptr;       // projection of general matrices: the transformed volume before the sum
     size_t proj_tmp_elems = 0;
     double* d_proj_part = nullptr;     // batched projection (kind 12): float64 partial sums [matrix][segment][h][w] of one launch (recycled like d_scratch_out);
-                                       // also the partials [segment][d][h][w] of a weighted box sum (kind 13)
+                                       // also the partials [segment][d][h][w] of a weighted box sum (kind 13) and [matrix][tile][3] of per-box scores (kind 14)
     size_t proj_part_bytes = 0;
     vt_volume* proj = nullptr;         // projection helper: 3 x H x W volume [S, S, S] sharing this handle's stream
     bool proj_sum_valid = false;       // the helper holds the weighted plane sum of (proj_sum_m3, proj_sum_oD, proj_sum_oplane0)

@@ -128,7 +128,7 @@ struct TilePlan {
     int kind;            // 1 direct, 2 tiled, 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled with packed footprints,
                          // 7 reserved (vt_volume_info: fused projection), 8 marching on plane quads, 9 lane-block tiles (cfg = row-stride index),
                          // 10 source rows along w (maps that leave axis 2 alone); vt_volume_info also reports 11 (batched box extraction),
-                         // 12 (batched projection) and 13 (weighted sum of boxes), which are planned by their own entry points
+                         // 12 (batched projection), 13 (weighted sum of boxes) and 14 (per-box template scores), which are planned by their own entry points
     int cfg;             // index into the tile table
     int td, th, tw;
     int lds_bytes;
@@ -302,6 +302,15 @@ void extract_sum_shape_plan(bool cubic, const int box[3], int n, int* cfg, int* 
 hipError_t init_extractsum_kernels();
 hipError_t launch_extract_sum(int cfg, int interp, const float* src, float* out, double* part, const float* zeros16,
                               const ExtractEntry* d_tab, const double* d_wts, int n, int per_seg, int nseg, const AffineParams& p,
+                              int lds_bytes, hipStream_t stream);
+
+// per-box template scores (vt_kernels_extractdot.hip, kind 14): extract_tiled's tiles and table entries; a workgroup reduces the three sums
+// of its (matrix, box tile) pair to one float64 triple in part[matrix][tile][3], a second kernel adds a box's tiles in ascending order
+// into out[matrix][3].  d_mask == nullptr: a mask of ones.  lds_bytes >= extract_dot_min_lds() (the cross-wave scratch overlays the box).
+int extract_dot_min_lds();
+hipError_t init_extractdot_kernels();
+hipError_t launch_extract_dot(int cfg, int interp, const float* src, double* out, double* part, const float* zeros16,
+                              const ExtractEntry* d_tab, const float* d_tmpl, const float* d_mask, int cnt, const AffineParams& p,
                               int lds_bytes, hipStream_t stream);
 
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.

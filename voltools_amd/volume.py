@@ -318,6 +318,102 @@ class StaticVolume:
             raise ValueError('weights must be finite and must not sum to 0')
         return self.extract_sum(ms, box_shape, w / total, profile, output)
 
+    # -- per-box template scores (extension: alignment search, template-matching refinement, classification; no reference counterpart) ----
+    def extract_dot(self, matrices: np.ndarray, template, mask=None, profile: bool = False, output=None, *,
+                    _flags: int = 0) -> Union[np.ndarray, None]:
+        """Three float64 sums over each box ``B_i = extract(matrices, template.shape)[i]`` without writing the boxes:
+        ``out[i] = (sum(mask * B_i), sum(mask * B_i**2), sum(template * B_i))``.  ``template`` (3-D; its shape is the box shape) and
+        ``mask`` (same shape; None = ones) are converted to contiguous float32 and must be finite.  Every sample is widened to float64
+        and added in a fixed order: ``out[i]`` depends on ``matrices[i]``, the template and the mask only, bit for bit, and repeated
+        calls give identical bits.  Returns a float64 array ``(n, 3)``, or fills ``output`` of that shape (C-contiguous numpy float64,
+        or a torch-ROCm float64 tensor on the volume's device) and returns None on a GPU device (``device='cpu'`` returns ``output``, like ``extract``).  float64 matrices keep their
+        precision; anything else is taken as float32."""
+        tmpl = np.ascontiguousarray(template, dtype=np.float32)
+        if tmpl.ndim != 3:
+            raise ValueError('template must be a 3-D array (its shape is the box shape)')
+        box = _box_shape(tmpl.shape)
+        msk = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+        if msk is not None and msk.shape != box:
+            raise ValueError(f'mask must have the template\'s shape {box}')
+        if not np.isfinite(tmpl).all() or (msk is not None and not np.isfinite(msk).all()):
+            raise ValueError('template and mask must be finite')
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] != (4, 4) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        n = ms.shape[0]
+        shape = (n, 3)
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.device == 'cpu':
+            if output is not None and not (isinstance(output, np.ndarray) and output.dtype == np.float64):
+                raise ValueError(f'output must be a float64 array of shape {shape}')
+            t_start = time.time()
+            boxes = self.extract(ms, box).astype(np.float64)
+            t64 = tmpl.astype(np.float64)
+            m64 = np.ones(box, dtype=np.float64) if msk is None else msk.astype(np.float64)
+            res = np.stack([(m64 * boxes).sum(axis=(1, 2, 3)), (m64 * boxes * boxes).sum(axis=(1, 2, 3)),
+                            (t64 * boxes).sum(axis=(1, 2, 3))], axis=1)
+            if profile:
+                print(f'{n} boxes scored in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = np.empty(shape, dtype=np.float64)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev, dtype=np.float64)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        mptr = None if msk is None else msk.ctypes.data
+        if ms.dtype == np.float64:
+            rc = self._lib.vt_volume_extract_dot_f64(self._handle, n, ms.ctypes.data, tmpl.ctypes.data, mptr, *box, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_extract_dot(self._handle, n, ms.ctypes.data, tmpl.ctypes.data, mptr, *box, ptr, flags)
+        _native.check(rc, 'vt_volume_extract_dot')
+        if profile:
+            print(f'{n} boxes scored in {self.timer_stop():.3f}ms')
+        return result
+
+    def correlate_at(self, positions, rotations=None, template=None, mask=None, rotation_units: str = 'deg',
+                     rotation_order: str = 'rzxz', profile: bool = False) -> np.ndarray:
+        """Locally normalised cross-correlation coefficient of ``template`` (under ``mask``; None = ones) with each of the boxes
+        ``extract_at(positions, rotations, template.shape)`` would cut, as float64 ``(n,)``.  On the host, in float64: ``N = sum(mask)``,
+        ``t = template - sum(mask * template) / N``, ``sigma_t = sqrt(sum(mask * t**2) / N)``; ``extract_dot`` with the template
+        ``float32(mask * t / (N * sigma_t))`` gives ``S0, S1, S2``, and ``cc = S2 / sqrt(S1 / N - (S0 / N)**2)`` (0 where the box has
+        no variance under the mask).  Because ``sum(mask * t) = 0`` the box mean needs no subtraction."""
+        if template is None:
+            raise ValueError('correlate_at needs a template')
+        t64 = np.asarray(template, dtype=np.float64)
+        if t64.ndim != 3:
+            raise ValueError('template must be a 3-D array (its shape is the box shape)')
+        m64 = np.ones(t64.shape, dtype=np.float64) if mask is None else np.asarray(mask, dtype=np.float32).astype(np.float64)   # the mask the kernel reads
+        if m64.shape != t64.shape:
+            raise ValueError(f'mask must have the template\'s shape {t64.shape}')
+        if not np.isfinite(t64).all() or not np.isfinite(m64).all():
+            raise ValueError('template and mask must be finite')
+        N = m64.sum()
+        if N == 0:
+            raise ValueError('the mask sums to 0')
+        that = t64 - (m64 * t64).sum() / N
+        sigma_t = np.sqrt((m64 * that * that).sum() / N)
+        if not sigma_t > 0:
+            raise ValueError('the template has no variance under the mask')
+        tmpl = (m64 * that / (N * sigma_t)).astype(np.float32)
+        ms = box_matrices(positions, rotations, t64.shape, rotation_units, rotation_order)
+        s = self.extract_dot(ms, tmpl, None if mask is None else m64.astype(np.float32), profile)
+        var = s[:, 1] / N - (s[:, 0] / N) ** 2
+        cc = np.zeros(s.shape[0], dtype=np.float64)
+        ok = var > 0
+        cc[ok] = s[ok, 2] / np.sqrt(var[ok])
+        return cc
+
     # -- projection (SURVEY 8(f)3; examples/projections.py:20-26 does transform(...).sum(axis=0)) -------
     def projection(self, transform_m: np.ndarray, profile: bool = False, output=None,
                    _flags: int = 0) -> Union[np.ndarray, None]:
