@@ -95,7 +95,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -253,6 +253,36 @@ int vt_volume_extract_dot(vt_volume_t* vol, int n, const float* m4x4s, const flo
                           int box_d, int box_h, int box_w, double* out /* n x 3 */, int flags);
 int vt_volume_extract_dot_f64(vt_volume_t* vol, int n, const double* m4x4s, const float* tmpl, const float* mask /* or NULL = all 1 */,
                               int box_d, int box_h, int box_w, double* out /* n x 3 */, int flags);
+
+/* ---- per-box scores against k templates: 2 + k float64 sums over each of n boxes, each box staged and sampled once ----
+ * out[i] = (sum_v mask[v] * B_i[v], sum_v mask[v] * B_i[v]^2, sum_v tmpls[0][v] * B_i[v], .., sum_v tmpls[k-1][v] * B_i[v]) with B_i as
+ * for vt_volume_extract_dot: what classifying n candidate poses against k references under one mask needs.  tmpls: k host float32 boxes
+ * of the box shape back to back in C order; mask: one such box, or NULL = all 1; both are uploaded on every call into a buffer the
+ * handle recycles.  out: n x (2 + k) float64 (host, or device with VT_OUT_DEVICE).
+ * Bit identity: for every j, columns 0, 1 and 2 + j hold exactly the bits vt_volume_extract_dot(vol, n, m4x4s, tmpls[j], mask, ..., flags)
+ * writes into its columns 0, 1, 2 -- on the default route, with VT_FORCE_TILED, with VT_FORCE_DIRECT, for entries that gather from global
+ * memory inside the tiled launch, on VT_EDGE_SCIPY handles and with a NULL mask.  The fused kernel (last_kernel 15 for every k, k = 1
+ * included) keeps vt_volume_extract_dot's roundings (exact products, (mask * b) * b rounded once, every addition rounded) and order (a
+ * thread's voxels in a fixed order, the tree of fixed shape over the 256 threads, the tiles of a box in ascending index by a second small
+ * kernel; no atomics), but stages each (matrix, box tile) and samples each (matrix, voxel) once, whatever k is: a thread holds the samples
+ * of its 4, 8 or 16 voxels in registers and accumulates the template sums three columns at a time.  A column is a fixed expression of
+ * (M_i, that template, mask, source, box shape, interpolation, route): it does not depend on n, on k, on the other templates, on the
+ * template's place in the stack, on the other matrices, on earlier calls or on host versus device output.  A box wholly outside gives a
+ * row of exact +0.
+ * The partials (box tiles x (2 + k) float64 per matrix) live in a buffer the handle recycles; a call whose partials would exceed 64 MiB
+ * is split into launches of at least one matrix each.  last_tile / last_lds_dims / last_lds_bytes as for vt_volume_extract, last_grid =
+ * box tiles x matrices of the last launch.  The handle's own output shape is neither read nor changed; VT_KEEP_OUTSIDE is ignored.
+ * Bounds: a box as for vt_volume_extract_dot ((box_d + 16) x box_h x box_w < 2^31: a voxel offset within one template has 32 bits;
+ * template j is addressed by a 64-bit base, so k x box voxels may exceed 2^31), and box tiles x (2 + k) < 2^31; beyond them
+ * VT_EUNSUPPORTED.  Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  Slab handles and
+ * handles not yet finalized: VT_EINVAL; k <= 0, n <= 0, NULL tmpls or out, non-positive box dims, non-finite matrix, template or mask
+ * entries: VT_EINVAL.  A refusal leaves the handle usable. */
+int vt_volume_extract_dot_multi(vt_volume_t* vol, int n, const float* m4x4s, int k, const float* tmpls /* k boxes, C order */,
+                                const float* mask /* or NULL = all 1 */, int box_d, int box_h, int box_w,
+                                double* out /* n x (2 + k) */, int flags);
+int vt_volume_extract_dot_multi_f64(vt_volume_t* vol, int n, const double* m4x4s, int k, const float* tmpls /* k boxes, C order */,
+                                    const float* mask /* or NULL = all 1 */, int box_d, int box_h, int box_w,
+                                    double* out /* n x (2 + k) */, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

@@ -33,6 +33,7 @@ SYMBOLS = [
     'vt_last_error', 'vt_version', 'vt_has_legacy_kernels', 'vt_volume_release_copies', 'vt_volume_set_max_resident',
     'vt_volume_extract', 'vt_volume_extract_f64', 'vt_volume_project_batch', 'vt_volume_project_batch_f64',
     'vt_volume_extract_sum', 'vt_volume_extract_sum_f64', 'vt_volume_extract_dot', 'vt_volume_extract_dot_f64',
+    'vt_volume_extract_dot_multi', 'vt_volume_extract_dot_multi_f64',
 ]
 
 
@@ -120,6 +121,8 @@ def load():
     L.vt_volume_extract_sum_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_extract_dot.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_extract_dot_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_extract_dot_multi.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_extract_dot_multi_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int]

@@ -274,6 +274,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_projbatch_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractsum_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractdot_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractdotmulti_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -2097,6 +2098,131 @@ int do_extract_dot(vt_volume* v, int n, const double* m4x4s, const float* tmpl, 
     return 0;
 }
 
+// n x (2 + k) float64: do_extract_dot's two mask sums followed by one template sum per template of the stack (scoring n candidate poses
+// against k references under one mask), in launches of kernel 15 (vt_kernels_extractdotmulti.hip), each followed by its small reduction
+// over the tiles of a box.  Every column holds the bits do_extract_dot gives for that template alone; each box is staged and sampled
+// once.  The boxes are never written.  Does not read or change the handle's own output shape.
+int do_extract_dot_multi(vt_volume* v, int n, const double* m4x4s, int k, const float* tmpls, const float* mask, int bd, int bh, int bw,
+                         double* out, int flags)
+{
+    if (!v || !m4x4s || !tmpls || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    if (k <= 0) return fail(VT_EINVAL, "template count %d", k);
+    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
+    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    if ((int64_t)(bd + 16) * bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");      // kernel 15 indexes a template / the mask with 32 bits
+    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
+    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
+        return fail(VT_EINVAL, "box scoring is available for whole-volume handles only (this one holds a slab window)");
+
+    const bool cubic = is_cubic(v->interp);
+    const int box[3] = {bd, bh, bw};
+    const int cfg = extract_pick_tile(cubic, box, nullptr);
+    int T[3];
+    extract_tile(cfg, &T[0], &T[1], &T[2]);
+    const int64_t tiles = (int64_t)((bd + T[0] - 1) / T[0]) * ((bh + T[1] - 1) / T[1]) * ((bw + T[2] - 1) / T[2]);
+    const int64_t ncol = 2 + (int64_t)k;
+    if (tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    if (tiles * ncol > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box tiles x (2 + k) = %lld exceeds 2^31 - 1", (long long)(tiles * ncol));
+
+    int rc = use_device(v->dev);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    const size_t n_box = (size_t)bd * bh * bw;
+    for (size_t j = 0; j < (size_t)k; ++j) {
+        const float* tj = tmpls + j * n_box;
+        for (size_t i = 0; i < n_box; ++i)
+            if (!std::isfinite(tj[i])) return fail(VT_EINVAL, "template %zu voxel %zu is not finite", j, i);
+    }
+    if (mask)
+        for (size_t i = 0; i < n_box; ++i)
+            if (!std::isfinite(mask[i])) return fail(VT_EINVAL, "mask voxel %zu is not finite", i);
+
+    const bool host_out = !(flags & VT_OUT_DEVICE);
+    const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
+
+    // the call's tables in one staging vector: one ExtractEntry per matrix, then the k templates back to back and the mask (float32,
+    // the stack and the mask padded to 16 bytes each)
+    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
+    const size_t per = sizeof(ExtractEntry) / sizeof(double);
+    const size_t stack_dbl = ((size_t)k * n_box + 3) / 4 * 2;      // doubles that hold the stack of float32 templates
+    const size_t box_dbl = (n_box + 3) / 4 * 2;                    // ... and one box
+    std::vector<double>& tab = v->h_batch_m;
+    tab.resize((size_t)n * per + stack_dbl + (mask ? box_dbl : 0));
+    int Lmax[3] = {0, 0, 0};
+    int64_t lds_bytes = extract_dot_min_lds();
+    for (int i = 0; i < n; ++i) {
+        const double* a = m4x4s + 16 * (size_t)i;
+        double m[12];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
+            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
+        }
+        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
+        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, e);
+        if (e->tiled) {
+            Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
+            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
+        }
+    }
+    std::memcpy(tab.data() + per * (size_t)n, tmpls, (size_t)k * n_box * sizeof(float));
+    if (mask) std::memcpy(tab.data() + per * (size_t)n + stack_dbl, mask, n_box * sizeof(float));
+    AffineParams p;
+    std::memset(&p, 0, sizeof(p));
+    TilePlan plan;
+    {
+        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
+        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
+    }
+    p.nTd = (bd + T[0] - 1) / T[0]; p.nTh = (bh + T[1] - 1) / T[1]; p.nTw = (bw + T[2] - 1) / T[2];
+
+    // matrices per launch: their partials stay within the cap (one matrix's partials at least), the grid within 2^31
+    const int64_t part_one = tiles * ncol * (int64_t)sizeof(double);
+    const int per_launch = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n, v->tune.dot_part_cap / part_one, 0x7fffffffLL / tiles}));
+    const size_t need = (size_t)per_launch * (size_t)part_one;
+    if (v->proj_part_bytes < need) {
+        if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
+        VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), need));
+        v->proj_part_bytes = need;
+    }
+    if (v->batch_m_cap < tab.size()) {
+        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
+        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
+        v->batch_m_cap = tab.size();
+    }
+    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
+                               hipMemcpyHostToDevice, v->stream));
+    const float* d_tmpls = reinterpret_cast<const float*>(v->d_batch_m + per * (size_t)n);
+    const float* d_mask = mask ? reinterpret_cast<const float*>(v->d_batch_m + per * (size_t)n + stack_dbl) : nullptr;
+    double* d_out = out;
+    const size_t out_bytes = (size_t)n * (size_t)ncol * sizeof(double);
+    PinnedScope pin(host_out ? out : nullptr, host_out ? out_bytes : 0);
+    if (host_out) {
+        float* d_stage = nullptr;
+        if ((rc = host_output_buffer(v, (size_t)n * (size_t)ncol * 2, &d_stage))) return rc;
+        d_out = reinterpret_cast<double*>(d_stage);
+    }
+
+    int last_cnt = 0;
+    for (int first = 0; first < n; first += per_launch) {
+        last_cnt = std::min(per_launch, n - first);
+        VT_HIP(launch_extract_dot_multi(cfg, v->interp, v->d_src, d_out + (size_t)first * (size_t)ncol, v->d_proj_part, v->d_zeros,
+                                        reinterpret_cast<const ExtractEntry*>(v->d_batch_m) + first, d_tmpls, d_mask, k, last_cnt, p,
+                                        (int)lds_bytes, v->stream));
+    }
+    v->last_kernel = 15;
+    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
+    v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
+    v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)(tiles * last_cnt);
+    if (host_out) {
+        VT_HIP(pin.copy(out, d_out, out_bytes, hipMemcpyDeviceToHost, v->stream));
+        VT_HIP(hipStreamSynchronize(v->stream));
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2470,6 +2596,22 @@ int vt_volume_extract_dot_f64(vt_volume_t* v, int n, const double* m4x4s, const 
                               double* out, int flags)
 {
     return do_extract_dot(v, n, m4x4s, tmpl, mask, box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_extract_dot_multi(vt_volume_t* v, int n, const float* m4x4s, int k, const float* tmpls, const float* mask, int box_d, int box_h,
+                                int box_w, double* out, int flags)
+{
+    if (!v || !m4x4s || !tmpls || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    std::vector<double> m((size_t)n * 16);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
+    return do_extract_dot_multi(v, n, m.data(), k, tmpls, mask, box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_extract_dot_multi_f64(vt_volume_t* v, int n, const double* m4x4s, int k, const float* tmpls, const float* mask, int box_d,
+                                    int box_h, int box_w, double* out, int flags)
+{
+    return do_extract_dot_multi(v, n, m4x4s, k, tmpls, mask, box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_project(vt_volume_t* v, const float* m4x4, float* out_hw, int flags)

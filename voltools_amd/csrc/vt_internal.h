@@ -313,6 +313,13 @@ hipError_t launch_extract_dot(int cfg, int interp, const float* src, double* out
                               const ExtractEntry* d_tab, const float* d_tmpl, const float* d_mask, int cnt, const AffineParams& p,
                               int lds_bytes, hipStream_t stream);
 
+// per-box scores against k templates (vt_kernels_extractdotmulti.hip, kind 15): launch_extract_dot's tiles, entries and LDS; d_tmpls holds k
+// boxes back to back; part[matrix][tile][2 + k], out[matrix][2 + k].  Column 2 + j holds launch_extract_dot's bits for template j.
+hipError_t init_extractdotmulti_kernels();
+hipError_t launch_extract_dot_multi(int cfg, int interp, const float* src, double* out, double* part, const float* zeros16,
+                                    const ExtractEntry* d_tab, const float* d_tmpls, const float* d_mask, int k, int cnt,
+                                    const AffineParams& p, int lds_bytes, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

@@ -414,6 +414,107 @@ class StaticVolume:
         cc[ok] = s[ok, 2] / np.sqrt(var[ok])
         return cc
 
+    # -- per-box scores against a stack of templates (extension: multi-reference classification and template matching) ----
+    def extract_dot_multi(self, matrices: np.ndarray, templates, mask=None, profile: bool = False, output=None, *,
+                          _flags: int = 0) -> Union[np.ndarray, None]:
+        """``extract_dot`` against K templates under one mask, each box staged and sampled once: ``out[i] = (sum(mask * B_i),
+        sum(mask * B_i**2), sum(templates[0] * B_i), .., sum(templates[K-1] * B_i))`` with ``B_i = extract(matrices, box)[i]``.
+        ``templates`` is 4-D ``(K, d, h, w)`` (``templates.shape[1:]`` is the box shape), ``mask`` has the box shape (None = ones); both
+        are converted to contiguous float32 and must be finite.  Columns 0, 1 and ``2 + j`` hold exactly the bits
+        ``extract_dot(matrices, templates[j], mask)`` gives in its columns 0, 1, 2: a column depends on ``matrices[i]``, its template and
+        the mask only.  Returns a float64 array ``(n, 2 + K)``, or fills ``output`` of that shape (C-contiguous numpy float64, or a
+        torch-ROCm float64 tensor on the volume's device) and returns None on a GPU device (``device='cpu'`` returns ``output``), like
+        ``extract_dot``.  float64 matrices keep their precision; anything else is taken as float32."""
+        tmpls = np.ascontiguousarray(templates, dtype=np.float32)
+        if tmpls.ndim != 4 or tmpls.shape[0] == 0:
+            raise ValueError('templates must be a non-empty 4-D stack (K, d, h, w); its trailing shape is the box shape')
+        K = tmpls.shape[0]
+        box = _box_shape(tmpls.shape[1:])
+        msk = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+        if msk is not None and msk.shape != box:
+            raise ValueError(f'mask must have the templates\' shape {box}')
+        if not np.isfinite(tmpls).all() or (msk is not None and not np.isfinite(msk).all()):
+            raise ValueError('templates and mask must be finite')
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] != (4, 4) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        n = ms.shape[0]
+        shape = (n, 2 + K)
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.device == 'cpu':
+            if output is not None and not (isinstance(output, np.ndarray) and output.dtype == np.float64):
+                raise ValueError(f'output must be a float64 array of shape {shape}')
+            t_start = time.time()
+            boxes = self.extract(ms, box).astype(np.float64)
+            m64 = np.ones(box, dtype=np.float64) if msk is None else msk.astype(np.float64)
+            cols = [(m64 * boxes).sum(axis=(1, 2, 3)), (m64 * boxes * boxes).sum(axis=(1, 2, 3))]
+            cols += [(tmpls[j].astype(np.float64) * boxes).sum(axis=(1, 2, 3)) for j in range(K)]      # extract_dot's expressions
+            res = np.stack(cols, axis=1)
+            if profile:
+                print(f'{n} boxes scored against {K} templates in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = np.empty(shape, dtype=np.float64)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev, dtype=np.float64)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        mptr = None if msk is None else msk.ctypes.data
+        if ms.dtype == np.float64:
+            rc = self._lib.vt_volume_extract_dot_multi_f64(self._handle, n, ms.ctypes.data, K, tmpls.ctypes.data, mptr, *box, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_extract_dot_multi(self._handle, n, ms.ctypes.data, K, tmpls.ctypes.data, mptr, *box, ptr, flags)
+        _native.check(rc, 'vt_volume_extract_dot_multi')
+        if profile:
+            print(f'{n} boxes scored against {K} templates in {self.timer_stop():.3f}ms')
+        return result
+
+    def correlate_templates_at(self, positions, rotations=None, templates=None, mask=None, rotation_units: str = 'deg',
+                               rotation_order: str = 'rzxz', profile: bool = False) -> np.ndarray:
+        """``correlate_at`` against K templates under one mask with one ``extract_dot_multi`` call: float64 ``(n, K)``, column ``j``
+        equal to ``correlate_at(positions, rotations, templates[j], mask)`` bit for bit.  Every template is normalised on the host as
+        ``correlate_at`` normalises its one (``N = sum(mask)``, ``t = template - sum(mask * template) / N``, ``sigma_t = sqrt(sum(mask *
+        t**2) / N)``, ``float32(mask * t / (N * sigma_t))``); then ``cc[i, j] = T_j / sqrt(S1 / N - (S0 / N)**2)``, 0 where the box has
+        no variance under the mask."""
+        if templates is None:
+            raise ValueError('correlate_templates_at needs templates')
+        t64 = np.asarray(templates, dtype=np.float64)
+        if t64.ndim != 4 or t64.shape[0] == 0:
+            raise ValueError('templates must be a non-empty 4-D stack (K, d, h, w); its trailing shape is the box shape')
+        box = t64.shape[1:]
+        m64 = np.ones(box, dtype=np.float64) if mask is None else np.asarray(mask, dtype=np.float32).astype(np.float64)   # the mask the kernel reads
+        if m64.shape != box:
+            raise ValueError(f'mask must have the templates\' shape {box}')
+        if not np.isfinite(t64).all() or not np.isfinite(m64).all():
+            raise ValueError('templates and mask must be finite')
+        N = m64.sum()
+        if N == 0:
+            raise ValueError('the mask sums to 0')
+        tmpls = np.empty(t64.shape, dtype=np.float32)
+        for j in range(t64.shape[0]):
+            that = t64[j] - (m64 * t64[j]).sum() / N
+            sigma_t = np.sqrt((m64 * that * that).sum() / N)
+            if not sigma_t > 0:
+                raise ValueError(f'template {j} has no variance under the mask')
+            tmpls[j] = (m64 * that / (N * sigma_t)).astype(np.float32)
+        ms = box_matrices(positions, rotations, box, rotation_units, rotation_order)
+        s = self.extract_dot_multi(ms, tmpls, None if mask is None else m64.astype(np.float32), profile)
+        var = s[:, 1] / N - (s[:, 0] / N) ** 2
+        cc = np.zeros((s.shape[0], t64.shape[0]), dtype=np.float64)
+        ok = var > 0
+        cc[ok] = s[ok, 2:] / np.sqrt(var[ok])[:, None]
+        return cc
+
     # -- projection (SURVEY 8(f)3; examples/projections.py:20-26 does transform(...).sum(axis=0)) -------
     def projection(self, transform_m: np.ndarray, profile: bool = False, output=None,
                    _flags: int = 0) -> Union[np.ndarray, None]:
