@@ -95,7 +95,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -283,6 +283,34 @@ int vt_volume_extract_dot_multi(vt_volume_t* vol, int n, const float* m4x4s, int
 int vt_volume_extract_dot_multi_f64(vt_volume_t* vol, int n, const double* m4x4s, int k, const float* tmpls /* k boxes, C order */,
                                     const float* mask /* or NULL = all 1 */, int box_d, int box_h, int box_w,
                                     double* out /* n x (2 + k) */, int flags);
+
+/* ---- g weighted sums of the same n extracted boxes, each box sampled once (class averages, half-set maps, bootstrap replicas) ----
+ * out: g boxes of box_d * box_h * box_w float32 back to back (host, or device with VT_OUT_DEVICE):
+ *     out[j][d, h, w] = float32(sum_i weights[i * g + j] * B_i[d, h, w])
+ * with B_i the float32 box vt_volume_extract writes for matrix i.  weights: n x g float64 in C order, required (there is no NULL form).
+ * Bit identity: for every j, box j holds exactly the bits vt_volume_extract_sum(vol, n, m4x4s, column j of weights, ..., flags) writes --
+ * on the default route, with VT_FORCE_TILED, with VT_FORCE_DIRECT, for entries that gather from global memory inside the tiled launch and
+ * on VT_EDGE_SCIPY handles -- provided every sample is finite: a matrix whose weights are all exactly 0 in a workgroup's share of the
+ * columns is passed over without being sampled, where vt_volume_extract_sum would add 0 x NaN for a non-finite sample.  A column is
+ * therefore a fixed expression of (matrices in their order, that column, source, box shape, interpolation, route): it does not depend on
+ * g, on the other columns, on the column's place in the matrix, on earlier calls or on host versus device output.
+ * The fused kernel (last_kernel 16 for every g, g = 1 included) keeps vt_volume_extract_sum's tile, segments of consecutive matrices,
+ * stepping, inside tests and per-sample expression; one workgroup serves a (segment, chunk of 2 / 4 / 8 consecutive columns for the
+ * 16^3 / 8x16x16 / 8x8x16 tile, box tile) triple, holds the samples of its threads' voxels in registers and adds each into the chunk's
+ * float64 accumulators.  No atomics.  last_tile / last_lds_dims / last_lds_bytes as for vt_volume_extract_sum; last_grid = workgroups of
+ * the last launch (box tiles x segments x column chunks of that launch).
+ * Device memory beyond the source: n x (192 + 8 g) bytes of tables and, with more than one segment, float64 partials of g x segments x box
+ * voxels in a buffer the handle recycles; a call whose partials would exceed 64 MiB is split into launches of whole column chunks (at
+ * least one), each followed by its reduction; the split does not show in the result.  The handle's own output shape is neither read nor
+ * changed; VT_KEEP_OUTSIDE is ignored.
+ * Bounds: the box as for vt_volume_extract_sum, and box tiles x segments x column chunks of a launch < 2^31; beyond them VT_EUNSUPPORTED.
+ * Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  Slab handles and handles not yet
+ * finalized: VT_EINVAL; n <= 0, g <= 0, NULL weights, non-positive box dims, non-finite matrix entries or weights: VT_EINVAL.  A refusal
+ * leaves the handle usable. */
+int vt_volume_extract_sum_multi(vt_volume_t* vol, int n, const float* m4x4s, int g, const double* weights /* n x g, C order */,
+                                int box_d, int box_h, int box_w, float* out /* g boxes, C order */, int flags);
+int vt_volume_extract_sum_multi_f64(vt_volume_t* vol, int n, const double* m4x4s, int g, const double* weights /* n x g, C order */,
+                                    int box_d, int box_h, int box_w, float* out /* g boxes, C order */, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

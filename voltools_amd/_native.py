@@ -34,6 +34,7 @@ SYMBOLS = [
     'vt_volume_extract', 'vt_volume_extract_f64', 'vt_volume_project_batch', 'vt_volume_project_batch_f64',
     'vt_volume_extract_sum', 'vt_volume_extract_sum_f64', 'vt_volume_extract_dot', 'vt_volume_extract_dot_f64',
     'vt_volume_extract_dot_multi', 'vt_volume_extract_dot_multi_f64',
+    'vt_volume_extract_sum_multi', 'vt_volume_extract_sum_multi_f64',
 ]
 
 
@@ -123,6 +124,8 @@ def load():
     L.vt_volume_extract_dot_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_extract_dot_multi.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_extract_dot_multi_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_extract_sum_multi.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_extract_sum_multi_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int]

@@ -320,6 +320,16 @@ hipError_t launch_extract_dot_multi(int cfg, int interp, const float* src, doubl
                                     const ExtractEntry* d_tab, const float* d_tmpls, const float* d_mask, int k, int cnt,
                                     const AffineParams& p, int lds_bytes, hipStream_t stream);
 
+// g weighted sums of the same n extracted boxes (vt_kernels_extractsummulti.hip, kind 16): launch_extract_sum's tile, entries, segments and
+// LDS; d_wts[i * g + j] for the gc columns of this launch (d_wts, out and part point at its first column); a workgroup owns a (segment,
+// chunk of extract_sum_multi_chunk(cfg) columns, box tile) triple.  With nseg > 1 the partials [column][segment][d][h][w] go through
+// launch_project_reduce(part, out, nseg, box voxels, gc, stream).  Box j holds launch_extract_sum's bits for column j.
+int extract_sum_multi_chunk(int cfg);
+hipError_t init_extractsummulti_kernels();
+hipError_t launch_extract_sum_multi(int cfg, int interp, const float* src, float* out, double* part, const float* zeros16,
+                                    const ExtractEntry* d_tab, const double* d_wts, int n, int per_seg, int nseg, int g, int gc,
+                                    const AffineParams& p, int lds_bytes, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

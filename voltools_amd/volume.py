@@ -318,6 +318,106 @@ class StaticVolume:
             raise ValueError('weights must be finite and must not sum to 0')
         return self.extract_sum(ms, box_shape, w / total, profile, output)
 
+    # -- G weighted sums of the same boxes (extension: class averages, half-set maps, bootstrap replicas; no reference counterpart) ----
+    def extract_sum_multi(self, matrices: np.ndarray, box_shape, weights, profile: bool = False, output=None, *,
+                          _flags: int = 0) -> Union[np.ndarray, None]:
+        """``G`` weighted sums of the same ``n`` boxes, each box sampled once: ``out[j] = float32(sum_i weights[i, j] *
+        extract(matrices, box_shape)[i])`` without writing the boxes.  ``weights``: shape ``(n, G)`` with G >= 1, converted to float64,
+        finite.  Box ``j`` holds the bits ``extract_sum(matrices, box_shape, weights[:, j])`` gives (all samples finite): it does not
+        depend on G, on the other columns or on the column's place.  Returns a float32 array ``(G, bd, bh, bw)``, or fills ``output`` of
+        that shape (numpy, ``vt.empty`` device array, torch-ROCm tensor) and returns None on a GPU device, like ``extract_sum``.
+        float64 matrices keep their precision; anything else is taken as float32."""
+        box = _box_shape(box_shape)
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] != (4, 4) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        n = ms.shape[0]
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 2 or w.shape[0] != n or w.shape[1] < 1:
+            raise ValueError(f'weights must have shape ({n}, G) with G >= 1')
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        g = w.shape[1]
+        shape = (g,) + box
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            data = self.data
+            if prefilter:       # what affine_transform(prefilter=True) does first (mode='constant'), once instead of per box
+                data = spline_filter(data, order, output=np.float64, mode='constant')
+            one = np.empty(box, dtype=self.data.dtype if np.issubdtype(self.data.dtype, np.floating) else np.float64)
+            acc = np.zeros(shape, dtype=np.float64)
+            t_start = time.time()
+            for i in range(n):
+                affine_transform(data, ms[i], output_shape=box, output=one, order=order, prefilter=False)
+                one64 = one.astype(np.float64)
+                for j in range(g):
+                    acc[j] += w[i, j] * one64
+            res = acc.astype(np.float32)
+            if profile:
+                print(f'{n} boxes summed into {g} in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        if ms.dtype == np.float64:
+            rc = self._lib.vt_volume_extract_sum_multi_f64(self._handle, n, ms.ctypes.data, g, w.ctypes.data, *box, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_extract_sum_multi(self._handle, n, ms.ctypes.data, g, w.ctypes.data, *box, ptr, flags)
+        _native.check(rc, 'vt_volume_extract_sum_multi')
+        if profile:
+            print(f'{n} boxes summed into {g} in {self.timer_stop():.3f}ms')
+        return result
+
+    def class_averages_at(self, positions, rotations=None, box_shape=None, labels=None, weights=None, n_classes=None,
+                          rotation_units: str = 'deg', rotation_order: str = 'rzxz', profile: bool = False,
+                          output=None) -> Union[np.ndarray, None]:
+        """``G`` weighted averages of the boxes ``extract_at`` would cut, in one ``extract_sum_multi`` call: the step of a classification
+        round that follows ``correlate_templates_at``.  Exactly one of ``labels`` (integers ``(n,)`` in ``[0, n_classes)``; ``n_classes``
+        defaults to ``max + 1``) or ``weights`` (``(n, G)`` float64) must be given.  Each column is divided by its sum on the host in
+        float64, as ``average_at`` does; a column whose sum is 0 stays all zero, so an empty class gives a zero box."""
+        ms = box_matrices(positions, rotations, box_shape, rotation_units, rotation_order)
+        n = ms.shape[0]
+        if (labels is None) == (weights is None):
+            raise ValueError('exactly one of labels and weights must be given')
+        if labels is not None:
+            lab = np.asarray(labels)
+            if lab.shape != (n,) or not np.issubdtype(lab.dtype, np.integer):
+                raise ValueError(f'labels must be integers of shape ({n},)')
+            g = int(lab.max()) + 1 if n_classes is None else int(n_classes)
+            if g < 1 or lab.min() < 0 or lab.max() >= g:
+                raise ValueError(f'labels must lie in [0, {g})')
+            w = np.zeros((n, g), dtype=np.float64)
+            w[np.arange(n), lab] = 1.0
+        else:
+            w = np.array(weights, dtype=np.float64)
+            if w.ndim != 2 or w.shape[0] != n or w.shape[1] < 1:
+                raise ValueError(f'weights must have shape ({n}, G) with G >= 1')
+            if n_classes is not None and int(n_classes) != w.shape[1]:
+                raise ValueError(f'n_classes = {n_classes} does not match weights of shape {w.shape}')
+            if not np.isfinite(w).all():
+                raise ValueError('weights must be finite')
+        total = w.sum(axis=0)
+        if not np.isfinite(total).all():
+            raise ValueError('weights must be finite')
+        nz = total != 0
+        w[:, nz] = w[:, nz] / total[nz]
+        w[:, ~nz] = 0.0
+        return self.extract_sum_multi(ms, box_shape, w, profile, output)
+
     # -- per-box template scores (extension: alignment search, template-matching refinement, classification; no reference counterpart) ----
     def extract_dot(self, matrices: np.ndarray, template, mask=None, profile: bool = False, output=None, *,
                     _flags: int = 0) -> Union[np.ndarray, None]:
