@@ -245,13 +245,15 @@ def _driving_axis(L, r):
     return int(np.argmax(np.abs(L[r])))
 
 
-def _face_offset(L, r, side, nsteps, shape, scipy):
+def _face_offset(L, r, side, nsteps, shape, scipy, src_shape=None):
     """Offset t_r for which the output voxel `nsteps` from the low / high end of the axis driving source axis r (the other two output
-    coordinates at their first voxel) has s_r exactly on the face, in exact arithmetic; float64 rounds it for the 3-4-5 parts."""
+    coordinates at their first voxel) has s_r exactly on the face, in exact arithmetic; float64 rounds it for the 3-4-5 parts.
+    `shape` is the OUTPUT extent; the source extent is `src_shape` where it differs (box cases)."""
+    src_shape = shape if src_shape is None else src_shape
     j = _driving_axis(L, r)
     x = np.zeros(3)
     x[j] = nsteps if (side == 'lo') == (L[r, j] > 0) else shape[j] - 1 - nsteps
-    lo, hi = (0.0, shape[r] - 1.0) if scipy else (-0.5, shape[r] - 0.5)
+    lo, hi = (0.0, src_shape[r] - 1.0) if scipy else (-0.5, src_shape[r] - 0.5)
     return (lo if side == 'lo' else hi) - float(L[r] @ x)
 
 
@@ -298,6 +300,85 @@ def cases(shape, groups=None):
     for spec in SPECS:
         if groups is None or spec['group'] in groups:
             yield place(spec, tuple(int(s) for s in shape))
+
+
+# ---------------------------------------------------------------------------------------------------
+# placing a spec on a box cut out of a larger volume (the box kernels, kinds 11-16)
+# ---------------------------------------------------------------------------------------------------
+BOX_TAP_MARGIN = 2          # a 'whole' box keeps every tap, the cubic ones included, this many voxels inside the volume
+
+
+def box_centre_of(box, kind):
+    """The box centre (box - 1) / 2 of an even-sized box for 'half', its floor for 'int'.  (On an odd extent 'half' still takes
+    floor + 0.5: a centre with integer and half-integer components breaks the lattice of the rotated parts.)"""
+    c = np.floor((np.asarray(box, np.float64) - 1.0) / 2.0)
+    return c if kind == 'int' else c + 0.5
+
+
+def _box_reach(L, cb, box):
+    """Per source axis the lowest and highest value of L @ (x - cb) over the box."""
+    hi_x = np.asarray(box, np.float64) - 1.0
+    lo = np.array([sum(min(L[r, k] * (0.0 - cb[k]), L[r, k] * (hi_x[k] - cb[k])) for k in range(3)) for r in range(3)])
+    hi = np.array([sum(max(L[r, k] * (0.0 - cb[k]), L[r, k] * (hi_x[k] - cb[k])) for k in range(3)) for r in range(3)])
+    return lo, hi
+
+
+def place_box(spec, shape, box):
+    """(name, m64, traits) of a spec on an output box cut out of a volume of `shape`.  The linear part turns about the box centre; the
+    centre samples a source position that keeps the lattice (integer, or half-integer for a 'half' spec) and puts the middle of the
+    box's footprint at the middle of the volume; the spec's base (its residue mod 4: what the alignment of the staged box's origin sees)
+    and eps go on top.  Face axes take the offset that puts an output plane / row / column on a face of the SOURCE volume."""
+    L = spec['L']
+    cb = box_centre_of(box, spec['centre'])
+    rlo, rhi = _box_reach(L, cb, box)
+    half = 0.0 if spec['centre'] == 'int' else 0.5
+    pos = np.floor((np.asarray(shape, np.float64) - 1.0) / 2.0 - (rlo + rhi) / 2.0 - 1.5) + half
+    t = pos - L @ cb
+    face = spec.get('face')
+    base = tuple(b % 4 for b in spec['base'])
+    for r in range(3):
+        if face and face[r]:
+            t[r] = _face_offset(L, r, face[r][0], face[r][1], box, spec['group'] == 'face_scipy', shape) + spec['eps'][r]
+        elif spec['group'] == 'f32twin':
+            k = np.float32(np.round(t[r]) + base[r])
+            t[r] = float(np.nextafter(k, np.float32(np.inf * spec['eps'][r]))) if spec['eps'][r] else float(k)
+        else:
+            t[r] = t[r] + base[r] + spec['eps'][r]
+    m = np.eye(4)
+    m[:3, :3] = L
+    m[:3, 3] = t
+    f32 = spec['group'] == 'f32twin'
+    if f32:
+        assert np.array_equal(m, m.astype(np.float32).astype(np.float64))
+    eps_axes = tuple(r for r in range(3) if spec['eps'][r] != 0.0) or \
+        ((0, 1, 2) if spec['eps_axis'] == 'all' else (spec['eps_axis'],))
+    grid = m[:3, 3] * 2.0 ** 41
+    exact = is_dyadic(L) and bool(np.all(grid == np.round(grid))) and max(max(shape), max(box)) < 2048
+    eps_mag = max(abs(e) for e in spec['eps'])
+    if f32:
+        eps_mag = float(max(abs(m[r, 3] - np.round(m[r, 3])) for r in eps_axes))
+    # whole: every tap of every voxel (floor - 1 .. floor + 2) at least BOX_TAP_MARGIN voxels inside the volume
+    zero = np.zeros(3)
+    flo, fhi = _box_reach(L, zero, box)
+    whole = all(t[r] + flo[r] >= BOX_TAP_MARGIN + 1.0 and t[r] + fhi[r] < shape[r] - 1.0 - BOX_TAP_MARGIN - 2.0 for r in range(3))
+    traits = dict(index=spec['index'], group=spec['group'], cls=spec['cls'], family=spec['family'], exact=exact, f32=f32,
+                  eps=spec['eps'], eps_mag=eps_mag, eps_axes=eps_axes, eps_axis=spec['eps_axis'],
+                  eps_sign=int(np.sign(next((e for e in spec['eps'] if e), 0.0))),
+                  share={r: 1.0 / lattice_period(L[r]) for r in eps_axes}, face=face, centre=spec['centre'],
+                  base=base, whole=bool(whole))
+    name = '%03d_%s_%s' % (spec['index'], spec['group'], spec['label'])
+    return name, m, traits
+
+
+def box_cases(shape, box, groups=None):
+    """Every sampled case placed on an output box `box` cut out of a volume `shape`, as (name, m64, traits); `traits['whole']` says
+    whether every tap lies BOX_TAP_MARGIN voxels inside the volume (lattice and f32twin cases, on boxes the volume has room for) or
+    the box is cut by a face (face cases, by construction)."""
+    shape = tuple(int(s) for s in shape)
+    box = tuple(int(s) for s in box)
+    for spec in SPECS:
+        if groups is None or spec['group'] in groups:
+            yield place_box(spec, shape, box)
 
 
 def chain_coords(m64, out_shape):

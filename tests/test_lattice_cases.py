@@ -139,6 +139,102 @@ def test_face_cases_hold_a_full_line_of_voxels_on_a_face():
                 assert np.any(s[r] == (lo if f[0] == 'lo' else hi)), name
 
 
+# ---- the same properties on box cases: an output box cut out of a larger volume (tests/test_gpu_box_lattice.py) ---------------------
+BOX_SOURCE = (96, 100, 104)
+BOXES = ((10, 18, 18), (10, 26, 18))          # the boxes of the GPU test (tests/test_box_index_model.py: which tile each selects)
+BOX_ALL = {box: list(lc.box_cases(BOX_SOURCE, box)) for box in BOXES}
+
+
+def _inside(m, box, src_shape, scipy=False):
+    s = lc.chain_coords(m, box)
+    ins = np.ones(box, bool)
+    for r in range(3):
+        lo, hi = (0.0, src_shape[r] - 1.0) if scipy else (-0.5, src_shape[r] - 0.5)
+        ins &= (s[r] >= lo) & ((s[r] <= hi) if scipy else (s[r] < hi))
+    return ins, s
+
+
+@pytest.mark.parametrize('box', BOXES, ids=lambda b: 'x'.join(map(str, b)))
+def test_box_cases_cover_every_class_eps_sign_and_axis(box):
+    """Placing a spec on a box keeps what the sample promises: every class of linear part meets every eps of either sign and every axis;
+    names are unique; everything but `whole` and the base (its residue mod 4) is what place() gives."""
+    cases = BOX_ALL[box]
+    lat = [t for _, _, t in cases if t['group'] == 'lattice']
+    for cls in lc.CLASSES:
+        mine = [t for t in lat if t['cls'] == cls]
+        seen_eps = {e for t in mine for e in t['eps'] if e} | ({0.0} if any(not any(t['eps']) for t in mine) else set())
+        assert seen_eps >= set(lc.EPS), (cls, sorted(set(lc.EPS) - seen_eps))
+        assert {t['base'][a] % 4 for t in mine for a in t['eps_axes']} == {0, 1, 2, 3}, cls
+        assert {t['eps_axis'] for t in mine} == {0, 1, 2, 'all'}, cls
+    assert len({n for n, _, _ in cases}) == len(cases) == len(ALL)
+    for (n0, _, t0), (n1, _, t1) in zip(ALL, cases):
+        assert n0 == n1
+        for key in ('index', 'group', 'cls', 'family', 'f32', 'eps', 'eps_axes', 'eps_axis', 'eps_sign', 'share', 'face', 'centre'):
+            assert t0[key] == t1[key], (n0, key)
+        assert all((a - b) % 4 == 0 for a, b in zip(t0['base'], t1['base'])), n0
+    assert all(t['exact'] for _, _, t in cases if t['group'] in ('face_exact', 'face_scipy'))
+    assert not any(t['exact'] for _, _, t in cases if t['group'] == 'face_chain')
+
+
+@pytest.mark.parametrize('box', BOXES, ids=lambda b: 'x'.join(map(str, b)))
+def test_box_cases_are_adversarial_and_whole_where_they_say(box):
+    """Share of box voxels within 2|eps| of an integer on every axis that received eps (as test_cases_are_adversarial; a box axis of n
+    voxels holds at least floor(n / q) of every q-th lattice plane, so the share is at least (1 - q / n) / q for the shortest axis n = 10
+    and the longest period q = 5: half of what the lattice predicts, asserted as such); lattice and float32-twin boxes lie, cubic taps
+    included, at least two voxels inside the volume, and `whole` says so for every case."""
+    n_whole = 0
+    for name, m, t in BOX_ALL[box]:
+        ins, s = _inside(m, box, BOX_SOURCE)
+        whole = all(s[r].min() >= lc.BOX_TAP_MARGIN + 1.0 and s[r].max() < BOX_SOURCE[r] - 1.0 - lc.BOX_TAP_MARGIN - 2.0 for r in range(3))
+        assert whole == t['whole'], (name, [(float(s[r].min()), float(s[r].max())) for r in range(3)])
+        n_whole += whole
+        if t['group'] in ('lattice', 'f32twin'):
+            assert whole and ins.all(), name
+            for r in t['eps_axes']:
+                window = 2.0 * (abs(m[r, 3] - np.round(m[r, 3])) if t['f32'] else abs(t['eps'][r])) + ROUNDING
+                share = float((np.abs(s[r] - np.round(s[r])) <= window).mean())
+                assert share >= 0.5 * t['share'][r], (name, r, share, t['share'][r])
+        elif t['group'] != 'face_scipy':
+            assert not whole, name                     # cut by construction
+    assert n_whole >= 200
+
+
+@pytest.mark.parametrize('box', BOXES, ids=lambda b: 'x'.join(map(str, b)))
+def test_box_face_cases_hold_a_full_line_of_voxels_on_a_face(box):
+    """As test_face_cases_hold_a_full_line_of_voxels_on_a_face, with the face of the SOURCE volume and the extent of the box."""
+    for name, m, t in BOX_ALL[box]:
+        if not t['group'].startswith('face'):
+            continue
+        s = lc.chain_coords(m, box)
+        for r, f in enumerate(t['face']):
+            if not f:
+                continue
+            lo, hi = (0.0, BOX_SOURCE[r] - 1.0) if t['group'] == 'face_scipy' else (-0.5, BOX_SOURCE[r] - 0.5)
+            on = np.abs(s[r] - (lo if f[0] == 'lo' else hi) - t['eps'][r]) <= FACE_BAND
+            assert any(bool(on.all(axis=a).any()) for a in range(3)), (name, r, f, int(on.sum()))
+            if t['eps'][r] == 0.0 and t['exact']:
+                assert np.any(s[r] == (lo if f[0] == 'lo' else hi)), name
+
+
+def test_oracle_is_nonzero_exactly_inside_on_positive_data():
+    """Source data in [1, 2): under trilinear and unfiltered cubic B-spline weights (non-negative, the nearest tap at least 1/8 per axis)
+    an inside voxel is strictly positive, so the oracle's zeros ARE its inside mask -- which a box result otherwise hides.  Asserted
+    for the oracle alone against the chain_coords inside set, on every texture-contract box case."""
+    vol = np.minimum(_vol(BOX_SOURCE, 5) + np.float32(1.0), np.nextafter(np.float32(2.0), np.float32(0.0))).astype(np.float32)
+    assert vol.min() >= 1.0 and vol.max() < 2.0
+    box = BOXES[0]
+    n_cut = 0
+    for name, m, t in BOX_ALL[box]:
+        if t['group'] == 'face_scipy':
+            continue
+        ins, _ = _inside(m, box, BOX_SOURCE)
+        n_cut += int(not ins.all())
+        for kind in ('linear', 'bspline', 'bspline_simple'):
+            want = oracle.affine_ex(vol, m, kind, box)
+            assert np.array_equal(want != 0, ins), (name, kind, int(((want != 0) != ins).sum()))
+    assert n_cut >= 50
+
+
 def test_oracle_matches_longdouble_reference():
     """`oracle.affine_ex` against the independent reference on every case, trilinear, cubic and cubic on prefiltered coefficients: within
     the family tolerance away from the faces; the same inside mask on chain-exact cases; on chain-dependent cases (3-4-5 and thirds

@@ -140,8 +140,20 @@ __device__ __forceinline__ bool blocked_tile(int t, int nTd, int nTh, int nTw, i
 // Q32.32 fixed-point coordinate: hi = integer part (box index), lo = fraction.  Stepping along the tile's
 // depth axis is two full-rate integer adds per axis instead of float64 arithmetic; the split into
 // (index, fraction) is free.  For ordinary matrices (float32 entries of moderate magnitude) the arithmetic
-// is exact; otherwise the drift is < 2^-29 voxel over a tile column.
+// is exact; otherwise to_fx truncates by less than one unit of 2^-32 and every step adds an increment rounded to
+// the nearest unit (|error| <= 1/2 unit), so over the 15 steps of a 16-deep tile column the coordinate drifts by
+// less than 8.5 * 2^-32 < 2^-28 voxel, IN EITHER DIRECTION.  A coordinate within that distance of an integer can
+// therefore have hi one below (fraction ~ 1) or one above (fraction ~ 0) the floor of the float64 coordinate: the
+// value is right to 2^-28 voxel, but the taps reach one element further than the float64 bounding box says.
+// The kernels that place a staged box by that bounding box keep kBoxMargin for it.
 struct Fx { int hi; unsigned lo; };
+
+// Origin and extent margin of the box kernels (kinds 11-16): o = floor(lo - kBoxMargin) - HALO puts every tap index at
+// or above 0 although the fixed-point coordinate of a voxel that sits exactly on floor(lo) may have drifted below it;
+// extract_box_dims sizes the box for an extent of ext + 2 kBoxMargin, which covers the lowered origin and the same
+// drift at the upper end.  Any value from 2^-28 up that is small against a voxel would do.  The shift is by a whole
+// voxel, so fractions -- and results -- are unchanged.  
+constexpr double kBoxMargin = 0x1p-24;
 
 __device__ __forceinline__ Fx to_fx(double x)
 {

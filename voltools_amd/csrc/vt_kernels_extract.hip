@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void extract_tiled(const float* __restrict__ s
     // integer origin of the staged box (finite and small: the tile meets the valid interval, its extent was bounded on the host)
     int o[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r]) - HALO;
+    for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;     // (vt_device.h: kBoxMargin)
     o[2] &= ~3;
 
     const int Lx = e.Lx, Ly = e.Ly, Lz = e.Lz;
@@ -193,7 +193,8 @@ static bool extract_box_dims(const double m[12], const int T[3], int halo2, int 
         double ext = 0;
         for (int k = 0; k < 3; ++k) ext += std::fabs(m[4 * r + k]) * (T[k] - 1);
         if (!(ext < 4096.0)) return false;
-        L[r] = (int)std::floor(ext) + 3 + halo2;             // floor(hi)-floor(lo) <= floor(ext)+1, +1 upper tap, +1 slack
+        // floor(hi + drift) - floor(lo - kBoxMargin) <= floor(ext + 2 kBoxMargin) + 1 origin indices, + 1 for the count, + 1 upper tap
+        L[r] = (int)std::floor(ext + 2.0 * kBoxMargin) + 3 + halo2;
     }
     L[2] = (L[2] + 3 + 3) & ~3;                              // origin aligned down by up to 3, stride multiple of 4
     return true;

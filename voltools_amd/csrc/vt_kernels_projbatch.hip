@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void project_tiled(const float* __restrict__ s
             // integer origin of the staged box (finite and small: the tile meets the valid interval, its extent was bounded on the host)
             int o[3];
 #pragma unroll
-            for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r]) - HALO;
+            for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;     // (vt_device.h: kBoxMargin)
             o[2] &= ~3;
 
             stage_box(lds, src, zeros16, p, o, Lz, Ly, Lx, tid);
