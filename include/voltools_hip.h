@@ -64,8 +64,11 @@ enum vt_flags {
                               instead of sampling the z-convolved copy (also what a call falls back to when that copy does not fit) */
     VT_NO_REORIENT = 32768,/* diagnostic: general matrices always sample the plain resident copy, never an axis-permuted one */
     VT_NO_ROWS = 65536,    /* diagnostic: maps that leave axis 2 alone take the axis-exchange path, not the row kernel (kind 10) */
-    VT_NO_PLANSHARE = 131072 /* diagnostic: the chunk layers of a cubic plane-quad launch on the z-convolved copy each build their
+    VT_NO_PLANSHARE = 131072,/* diagnostic: the chunk layers of a cubic plane-quad launch on the z-convolved copy each build their
                               tile's staging plan instead of sharing one per tile (same results) */
+    VT_ACCUMULATE = 262144,/* vt_volume_place only: the sums start from `out` as found instead of +0; voxels of tiles no copy can reach
+                              are neither read nor written */
+    VT_PLACE_DENSE = 524288/* vt_volume_place only, diagnostic: every matrix is listed for every output tile (same results) */
 };
 
 /* flags for vt_volume_create* */
@@ -95,7 +98,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -311,6 +314,35 @@ int vt_volume_extract_sum_multi(vt_volume_t* vol, int n, const float* m4x4s, int
                                 int box_d, int box_h, int box_w, float* out /* g boxes, C order */, int flags);
 int vt_volume_extract_sum_multi_f64(vt_volume_t* vol, int n, const double* m4x4s, int g, const double* weights /* n x g, C order */,
                                     int box_d, int box_h, int box_w, float* out /* g boxes, C order */, int flags);
+
+/* ---- n posed, weighted copies of the resident map summed into one (usually much larger) map: "place-back" model tomograms from refined
+ * poses, synthetic tomograms, and, with negative weights and VT_ACCUMULATE, subtraction of picked particles from a tomogram.  The handle
+ * holds the small map T (any shape, any interpolation, VT_EDGE_SCIPY handles included).  m4x4s: n x 16 pull matrices, output voxel index ->
+ * T coordinate, s = P_i[:3,:3] . (d,h,w) + P_i[:3,3].  out: out_d * out_h * out_w float32 (host, or device with VT_OUT_DEVICE):
+ *     out[v] = float32(b[v] + w_0 * A_0[v] + w_1 * A_1[v] + ...)        ascending i, only the i listed for the tile of v
+ * with A_i the float32 volume vt_volume_affine would write for P_i at that output shape (the handle's interpolation and boundary contract,
+ * 0 outside).  weights: n float64, or NULL for all 1.  Each term is widened to float64, multiplied by its float64 weight and added
+ * to a float64 accumulator by vt_volume_extract_sum's accumulation step (the same function text compiled with the same options, so the
+ * same instructions); the sum is rounded to float32 once.  b[v] is +0, or with VT_ACCUMULATE double(out[v]) as found.
+ * The output is cut into the tiles vt_volume_extract_sum uses for a box of that shape; the host lists for every tile the matrices whose
+ * copy can reach it (a superset of those that do: the kernel still tests each listed one, so an over-listed matrix adds nothing) and ONE
+ * workgroup per non-empty tile (last_kernel 17) walks its list in ascending i.  A voxel whose tile has an empty list is +0 by default (one
+ * memset of the output precedes the launch); with VT_ACCUMULATE it is neither read nor written -- NaN, -0 and everything else keep their
+ * bits.  No segments, no atomics: the expression does not depend on n, on the binning or on what the handle did before.
+ * Identity: wherever vt_volume_extract_sum(vol, n, m4x4s, weights, out_d, out_h, out_w, out, flags) runs one segment (1024 tiles or more)
+ * this call without VT_ACCUMULATE writes the same bits, up to the sign of a zero.  VT_PLACE_DENSE lists every matrix for every tile
+ * (same bits); VT_FORCE_DIRECT makes every matrix gather from global memory inside the same kernel, as matrices whose tile footprint fits
+ * no LDS box always do; VT_FORCE_TILED selects the same kernel as the default; VT_KEEP_OUTSIDE is ignored.
+ * last_grid = non-empty tiles launched (0: no kernel ran); last_tile / last_lds_dims / last_lds_bytes as for vt_volume_extract_sum.
+ * Device memory beyond the source: n x 200 bytes of tables, 8 bytes per non-empty tile and 4 bytes per list entry, in a buffer the
+ * handle recycles.  Output tiles and the total list length must stay below 2^31: VT_EUNSUPPORTED beyond.
+ * Host `out`: returns after the copy back (with VT_ACCUMULATE the caller's array is uploaded first); VT_OUT_DEVICE: asynchronous on the
+ * handle's stream.  Slab handles and handles not yet finalized: VT_EINVAL; n <= 0, non-positive dims, non-finite matrix entries or
+ * weights: VT_EINVAL. */
+int vt_volume_place(vt_volume_t* vol, int n, const float* m4x4s, const double* weights /* n, or NULL = all 1 */,
+                    int out_d, int out_h, int out_w, float* out, int flags);
+int vt_volume_place_f64(vt_volume_t* vol, int n, const double* m4x4s, const double* weights /* n, or NULL = all 1 */,
+                        int out_d, int out_h, int out_w, float* out, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

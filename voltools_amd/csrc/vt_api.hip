@@ -276,6 +276,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractdot_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractdotmulti_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractsummulti_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_place_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -2341,6 +2342,198 @@ int do_extract_sum_multi(vt_volume* v, int n, const double* m4x4s, int g, const 
     return 0;
 }
 
+// Output tiles whose base can pass place_tiled's tile test (any_valid) for entry e, as an axis-aligned range of tile indices per axis
+// (t_lo[k] > t_hi[k]: none).  The test accepts a tile base y = A x0 + t iff vlo - kTileMargin - pos <= y < vhi + kTileMargin - neg on
+// every row; the inverse image of that box under A is a parallelepiped whose bounding box (the 8 corners, taken term by term) is widened
+// by 1 + 1e-6 max|bound| voxels -- far more than float64 rounding moves a bound once A is accepted below -- and cut to whole tiles.
+// Every tile, whatever the matrix: a 3 x 3 part with a zero row, a non-finite determinant or |det A| < 1e-6 |row 0| |row 1| |row 2| (the
+// rows span less than a millionth of the volume their lengths allow: the inverse would amplify rounding by more than the slack covers),
+// or non-finite bounds.  Nothing is divided before A has passed that test.  Direct (untiled) entries use the same range: their per-voxel
+// inside test implies the tile test up to rounding that the margins cover.
+void place_tile_range(const ExtractEntry& e, const AffineParams& p, const int T[3], const int nT[3], int t_lo[3], int t_hi[3])
+{
+    for (int k = 0; k < 3; ++k) { t_lo[k] = 0; t_hi[k] = nT[k] - 1; }
+    const double* m = e.m;
+    const double a[3][3] = {{m[0], m[1], m[2]}, {m[4], m[5], m[6]}, {m[8], m[9], m[10]}};
+    double norm[3];
+    for (int r = 0; r < 3; ++r) norm[r] = std::sqrt(a[r][0] * a[r][0] + a[r][1] * a[r][1] + a[r][2] * a[r][2]);
+    const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1], c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2], c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];
+    const double det = a[0][0] * c00 + a[0][1] * c01 + a[0][2] * c02;
+    const double span = norm[0] * norm[1] * norm[2];
+    if (!std::isfinite(det) || !std::isfinite(span) || !(span > 0.0) || !(std::fabs(det) >= 1.0e-6 * span)) return;
+    const double inv[3][3] = {
+        {c00 / det, (a[0][2] * a[2][1] - a[0][1] * a[2][2]) / det, (a[0][1] * a[1][2] - a[0][2] * a[1][1]) / det},
+        {c01 / det, (a[0][0] * a[2][2] - a[0][2] * a[2][0]) / det, (a[0][2] * a[1][0] - a[0][0] * a[1][2]) / det},
+        {c02 / det, (a[0][1] * a[2][0] - a[0][0] * a[2][1]) / det, (a[0][0] * a[1][1] - a[0][1] * a[1][0]) / det}};
+    double y_lo[3], y_hi[3];
+    for (int r = 0; r < 3; ++r) {
+        y_lo[r] = p.vlo[r] - kTileMargin - e.pos[r] - m[4 * r + 3];
+        y_hi[r] = p.vhi[r] + kTileMargin - e.neg[r] - m[4 * r + 3];
+    }
+    int lo_i[3], hi_i[3];
+    for (int k = 0; k < 3; ++k) {
+        double lo = 0.0, hi = 0.0;
+        for (int r = 0; r < 3; ++r) {
+            const double u = inv[k][r] * y_lo[r], w = inv[k][r] * y_hi[r];
+            lo += std::min(u, w); hi += std::max(u, w);
+        }
+        if (!std::isfinite(lo) || !std::isfinite(hi)) return;
+        const double pad = 1.0 + 1.0e-6 * std::max(std::fabs(lo), std::fabs(hi));
+        const double first = std::ceil((lo - pad) / T[k]), last = std::floor((hi + pad) / T[k]);
+        lo_i[k] = (int)std::max(0.0, std::min(first, (double)nT[k]));
+        hi_i[k] = (int)std::min((double)(nT[k] - 1), std::max(last, -1.0));
+    }
+    for (int k = 0; k < 3; ++k) { t_lo[k] = lo_i[k]; t_hi[k] = hi_i[k]; }
+}
+
+// One map of shape (od, oh, ow): n weighted copies of the resident map, each through its own pull matrix, summed in float64 in ascending
+// order and rounded once -- do_extract_sum's expression with the output as "the box", but only where a copy can land: the entries are
+// binned into per-tile lists here, and kernel 17 (vt_kernels_place.hip) runs one workgroup per tile with a non-empty list.  VT_ACCUMULATE
+// starts the sums from `out` as found and leaves the other tiles alone; otherwise `out` is zeroed first.  Does not read or change the
+// handle's own output shape.
+int do_place(vt_volume* v, int n, const double* m4x4s, const double* weights, int od, int oh, int ow, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    if (od <= 0 || oh <= 0 || ow <= 0) return fail(VT_EINVAL, "non-positive output dims (%d,%d,%d)", od, oh, ow);
+    if ((int64_t)od * oh > 0x7fffffffLL || (int64_t)oh * ow > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
+    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
+    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
+        return fail(VT_EINVAL, "placing copies is available for whole-volume handles only (this one holds a slab window)");
+    int rc = use_device(v->dev);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    if (weights)
+        for (int i = 0; i < n; ++i)
+            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %d is not finite", i);
+
+    const bool cubic = is_cubic(v->interp);
+    const int shape[3] = {od, oh, ow};
+    const size_t n_out = (size_t)od * oh * ow;
+    const bool host_out = !(flags & VT_OUT_DEVICE);
+    const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
+    const bool accumulate = (flags & VT_ACCUMULATE) != 0;
+    const bool dense = (flags & VT_PLACE_DENSE) != 0;
+    const int cfg = extract_pick_tile(cubic, shape, nullptr);      // a function of (output shape, interpolation): do_extract_sum's tile
+    int T[3];
+    extract_tile(cfg, &T[0], &T[1], &T[2]);
+    const int nT[3] = {(od + T[0] - 1) / T[0], (oh + T[1] - 1) / T[1], (ow + T[2] - 1) / T[2]};
+    const int64_t tiles = (int64_t)nT[0] * nT[1] * nT[2];
+    if (tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large (%lld tiles)", (long long)tiles);
+
+    // the launch's tables: one ExtractEntry per matrix, then the n weights, then (below) the lists
+    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
+    const size_t per = sizeof(ExtractEntry) / sizeof(double);
+    std::vector<double>& tab = v->h_batch_m;
+    tab.resize((size_t)n * (per + 1));
+    int Lmax[3] = {0, 0, 0};
+    int64_t lds_bytes = 16;
+    for (int i = 0; i < n; ++i) {
+        const double* a = m4x4s + 16 * (size_t)i;
+        double m[12];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
+            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
+        }
+        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
+        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, e);
+        if (e->tiled) {
+            Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
+            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
+        }
+        tab[per * (size_t)n + (size_t)i] = weights ? weights[i] : 1.0;
+    }
+    AffineParams p;
+    std::memset(&p, 0, sizeof(p));
+    TilePlan plan;
+    {
+        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, od, oh, ow, true);
+        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, output dims, valid interval
+    }
+    p.nTd = nT[0]; p.nTh = nT[1]; p.nTw = nT[2];
+
+    // ---- binning: count, then fill, both in ascending entry order, so every list is ascending by construction; O(sum of candidate tiles) ----
+    std::vector<int> range((size_t)n * 6);
+    std::vector<int> cursor((size_t)tiles, 0);        // per tile: entries listed, then the write position of its list
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        int* lo = &range[6 * (size_t)i];
+        int* hi = lo + 3;
+        if (dense) for (int k = 0; k < 3; ++k) { lo[k] = 0; hi[k] = nT[k] - 1; }
+        else place_tile_range(*reinterpret_cast<const ExtractEntry*>(tab.data() + per * (size_t)i), p, T, nT, lo, hi);
+        if (lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) { lo[0] = 0; hi[0] = -1; continue; }
+        total += (int64_t)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1);
+        if (total > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "tile lists too long (more than 2^31 - 1 (tile, matrix) pairs)");
+        for (int a = lo[0]; a <= hi[0]; ++a)
+            for (int b = lo[1]; b <= hi[1]; ++b) {
+                int* row = &cursor[((size_t)a * nT[1] + b) * nT[2]];
+                for (int c = lo[2]; c <= hi[2]; ++c) ++row[c];
+            }
+    }
+    int64_t n_tiles = 0;
+    for (int64_t t = 0; t < tiles; ++t) n_tiles += cursor[(size_t)t] > 0;
+    const size_t ints = n_tiles > 0 ? (size_t)(2 * n_tiles + 1 + total) : 0;      // tile ids, offsets, list entries
+    const size_t ints_at = (size_t)n * (per + 1);
+    tab.resize(ints_at + (ints + 1) / 2);
+    int* const ids = reinterpret_cast<int*>(tab.data() + ints_at);
+    int* const offs = ids + n_tiles;
+    int* const idx = offs + n_tiles + 1;
+    if (n_tiles > 0) {
+        int64_t k = 0, at = 0;
+        for (int64_t t = 0; t < tiles; ++t) {
+            const int cnt = cursor[(size_t)t];
+            if (cnt == 0) continue;
+            ids[k] = (int)t; offs[k] = (int)at; ++k;
+            cursor[(size_t)t] = (int)at;
+            at += cnt;
+        }
+        offs[n_tiles] = (int)at;
+        for (int i = 0; i < n; ++i) {
+            const int* lo = &range[6 * (size_t)i];
+            const int* hi = lo + 3;
+            for (int a = lo[0]; a <= hi[0]; ++a)
+                for (int b = lo[1]; b <= hi[1]; ++b) {
+                    int* row = &cursor[((size_t)a * nT[1] + b) * nT[2]];
+                    for (int c = lo[2]; c <= hi[2]; ++c) idx[row[c]++] = i;
+                }
+        }
+    }
+
+    v->last_kernel = 17;
+    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
+    v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
+    v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)n_tiles;
+    if (n_tiles == 0 && accumulate) return 0;          // nothing can land anywhere: `out` stays as found, nothing is launched
+
+    float* d_out = out;
+    PinnedScope pin(host_out ? out : nullptr, host_out ? n_out * sizeof(float) : 0);       // the caller's array: in (accumulate) and out
+    if (host_out) {
+        if ((rc = host_output_buffer(v, n_out, &d_out))) return rc;
+        if (accumulate) VT_HIP(pin.copy(d_out, out, n_out * sizeof(float), hipMemcpyHostToDevice, v->stream));
+    }
+    if (!accumulate) VT_HIP(hipMemsetAsync(d_out, 0, n_out * sizeof(float), v->stream));
+    if (n_tiles > 0) {                                // (a grid of 0 is an error)
+        if (v->batch_m_cap < tab.size()) {
+            if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
+            VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
+            v->batch_m_cap = tab.size();
+        }
+        VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
+                                   hipMemcpyHostToDevice, v->stream));
+        const int* d_ids = reinterpret_cast<const int*>(v->d_batch_m + ints_at);
+        VT_HIP(launch_place(cfg, v->interp, v->d_src, d_out, v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m),
+                            v->d_batch_m + per * (size_t)n, d_ids, d_ids + n_tiles, d_ids + 2 * n_tiles + 1, (int)n_tiles, accumulate, p,
+                            (int)lds_bytes, v->stream));
+    }
+    if (host_out) {
+        VT_HIP(pin.copy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+        VT_HIP(hipStreamSynchronize(v->stream));
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2714,6 +2907,21 @@ int vt_volume_extract_sum_multi_f64(vt_volume_t* v, int n, const double* m4x4s, 
                                     float* out, int flags)
 {
     return do_extract_sum_multi(v, n, m4x4s, g, weights, box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_place(vt_volume_t* v, int n, const float* m4x4s, const double* weights, int out_d, int out_h, int out_w, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    std::vector<double> m((size_t)n * 16);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
+    return do_place(v, n, m.data(), weights, out_d, out_h, out_w, out, flags);
+}
+
+int vt_volume_place_f64(vt_volume_t* v, int n, const double* m4x4s, const double* weights, int out_d, int out_h, int out_w, float* out,
+                        int flags)
+{
+    return do_place(v, n, m4x4s, weights, out_d, out_h, out_w, out, flags);
 }
 
 int vt_volume_extract_dot(vt_volume_t* v, int n, const float* m4x4s, const float* tmpl, const float* mask, int box_d, int box_h, int box_w,

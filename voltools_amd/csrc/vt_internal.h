@@ -330,6 +330,15 @@ hipError_t launch_extract_sum_multi(int cfg, int interp, const float* src, float
                                     const ExtractEntry* d_tab, const double* d_wts, int n, int per_seg, int nseg, int g, int gc,
                                     const AffineParams& p, int lds_bytes, hipStream_t stream);
 
+// n posed, weighted copies of the resident map summed into one output (vt_kernels_place.hip, kind 17): launch_extract_sum's tile, entries and
+// LDS with the output as "the box", one workgroup per NON-EMPTY output tile.  d_tile_ids: the n_tiles (> 0) tile ids that have a list;
+// d_offs: n_tiles + 1 ascending offsets into d_idx; d_idx: entry indices, ascending per tile.  accumulate: sums start from `out` as found.
+// Tiles without a list are not touched: the caller zeroes `out` first unless it accumulates.
+hipError_t init_place_kernels();
+hipError_t launch_place(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
+                        const double* d_wts, const int* d_tile_ids, const int* d_offs, const int* d_idx, int n_tiles, bool accumulate,
+                        const AffineParams& p, int lds_bytes, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

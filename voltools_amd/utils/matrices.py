@@ -155,6 +155,35 @@ def box_matrices(positions, rotations=None, box_shape=None, rotation_units: str 
     return ms
 
 
+def place_matrices(positions, rotations=None, box_shape=None, rotation_units: str = 'deg',
+                   rotation_order: str = 'rzxz') -> np.ndarray:
+    """Pull matrices (n, 4, 4), float64, that put ``n`` copies of a map of shape ``box_shape`` into a larger one
+    (``StaticVolume.place``): the exact inverses of ``box_matrices(positions, rotations, box_shape, ...)``.
+
+    With ``c = (box_shape - 1) / 2`` and ``R_i`` as in ``box_matrices``: ``P_i[:3, :3] = R_i^T`` and ``P_i[:3, 3] = c - R_i^T .
+    positions[i]``, so output voxel ``positions[i]`` samples the centre of the map: copy ``i`` has its centre at ``positions[i]``, in
+    the orientation that ``extract_at(positions, rotations)`` would undo.
+    """
+    box = _box_shape(box_shape)
+    pos = np.asarray(positions, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3 or pos.shape[0] == 0:
+        raise ValueError('positions must have shape (n, 3)')
+    n = pos.shape[0]
+    if rotations is not None:
+        rot = np.asarray(rotations, dtype=np.float64)
+        if rot.ndim != 2 or rot.shape[1] != 3 or rot.shape[0] != n:
+            raise ValueError('rotations must have shape (n, 3), one per position')
+    c = (np.asarray(box, dtype=np.float64) - 1.0) / 2.0
+    ms = np.zeros((n, 4, 4), dtype=np.float64)
+    for i in range(n):
+        r3 = np.identity(3, dtype=np.float64) if rotations is None else \
+            rotation_matrix(rot[i], rotation_units, rotation_order, dtype=np.float64)[:3, :3]
+        ms[i, :3, :3] = r3.T
+        ms[i, :3, 3] = c - r3.T @ pos[i]
+        ms[i, 3, 3] = 1.0
+    return ms
+
+
 def tilt_matrices(angles, tilt_axis: int = 1, shape=None, rotation_units: str = 'deg', center: Vec3 = None) -> np.ndarray:
     """Pull matrices (n, 4, 4) of a tilt series of a volume of shape ``shape`` (``StaticVolume.tilt_series``): matrix ``i`` is
     ``transform_matrix(rotation=r, rotation_order='sxyz', center=center)`` with ``r`` zero except ``r[tilt_axis] = angles[i]``,

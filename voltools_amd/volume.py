@@ -14,7 +14,7 @@ from scipy.ndimage import affine_transform, spline_filter
 
 from . import _native
 from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
-from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, tilt_matrices,
+from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, place_matrices, tilt_matrices,
                     get_available_devices, switch_to_device)
 from .utils.matrices import _box_shape
 
@@ -317,6 +317,80 @@ class StaticVolume:
         if not np.isfinite(w).all() or total == 0:
             raise ValueError('weights must be finite and must not sum to 0')
         return self.extract_sum(ms, box_shape, w / total, profile, output)
+
+    # -- posed, weighted copies of this map summed into one larger map (extension: place-back, synthetic tomograms, particle subtraction) ----
+    def place(self, matrices: np.ndarray, output_shape, weights=None, profile: bool = False, output=None, *,
+              accumulate: bool = False, _flags: int = 0) -> Union[np.ndarray, None]:
+        """``n`` copies of this volume put into one map of shape ``output_shape = (oD, oH, oW)``, copy ``i`` through its pull matrix
+        (output voxel index -> coordinate in this volume, ``src = P_i[:3, :3] . (d, h, w) + P_i[:3, 3]``; ``utils.place_matrices`` builds
+        them from positions and rotations): ``out = float32(b + sum_i weights[i] * A_i)`` with ``A_i`` what ``affine(matrices[i])`` would
+        return at that output shape (0 outside the copy) and ``b`` zero, or with ``accumulate=True`` the contents of ``output``, which is
+        then required (negative weights subtract copies from a map).  Every term is widened to float64, multiplied by its float64 weight
+        and added in float64, in the order of ``matrices``; the sum is rounded to float32 once: ``extract_sum(matrices, output_shape,
+        weights)`` evaluates the same expression.  On a GPU device only the output tiles a copy can reach are computed, so the cost
+        follows the volume covered, not ``n`` x the output volume; with ``accumulate`` every voxel outside those tiles keeps its bits.
+        ``weights``: shape ``(n,)``, converted to float64; None = ones.  Returns a float32 array ``(oD, oH, oW)``, or fills ``output`` of
+        that shape (numpy, ``vt.empty`` device array, torch-ROCm tensor) and returns None on a GPU device, like ``extract_sum``.  Repeated
+        calls give identical bits.  float64 matrices keep their precision; anything else is taken as float32."""
+        shape = _box_shape(output_shape)
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] != (4, 4) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        n = ms.shape[0]
+        w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f'weights must have shape ({n},)')
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        if accumulate and output is None:
+            raise ValueError('accumulate=True adds into output, which must be given')
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            data = self.data
+            if prefilter:       # what affine_transform(prefilter=True) does first (mode='constant'), once instead of per copy
+                data = spline_filter(data, order, output=np.float64, mode='constant')
+            one = np.empty(shape, dtype=self.data.dtype if np.issubdtype(self.data.dtype, np.floating) else np.float64)
+            acc = np.asarray(output).astype(np.float64) if accumulate else np.zeros(shape, dtype=np.float64)
+            t_start = time.time()
+            for i in range(n):
+                affine_transform(data, ms[i], output_shape=shape, output=one, order=order, prefilter=False)
+                acc += w[i] * one.astype(np.float64)
+            res = acc.astype(np.float32)
+            if profile:
+                print(f'{n} copies placed in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags | (_native.ACCUMULATE if accumulate else 0)
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        if ms.dtype == np.float64:
+            rc = self._lib.vt_volume_place_f64(self._handle, n, ms.ctypes.data, w.ctypes.data, *shape, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_place(self._handle, n, ms.ctypes.data, w.ctypes.data, *shape, ptr, flags)
+        _native.check(rc, 'vt_volume_place')
+        if profile:
+            print(f'{n} copies placed in {self.timer_stop():.3f}ms')
+        return result
+
+    def place_at(self, positions, rotations=None, output_shape=None, weights=None, rotation_units: str = 'deg',
+                 rotation_order: str = 'rzxz', profile: bool = False, output=None, *, accumulate: bool = False) -> Union[np.ndarray, None]:
+        """``place`` of copies centred at ``positions`` (n, 3) of the output, copy ``i`` in the orientation ``extract_at(positions,
+        rotations)`` would undo (none: axis-aligned): the matrices of ``utils.place_matrices`` for this volume's shape, in float64."""
+        return self.place(place_matrices(positions, rotations, self.shape, rotation_units, rotation_order), output_shape, weights,
+                          profile, output, accumulate=accumulate)
 
     # -- G weighted sums of the same boxes (extension: class averages, half-set maps, bootstrap replicas; no reference counterpart) ----
     def extract_sum_multi(self, matrices: np.ndarray, box_shape, weights, profile: bool = False, output=None, *,
