@@ -66,8 +66,8 @@ enum vt_flags {
     VT_NO_ROWS = 65536,    /* diagnostic: maps that leave axis 2 alone take the axis-exchange path, not the row kernel (kind 10) */
     VT_NO_PLANSHARE = 131072,/* diagnostic: the chunk layers of a cubic plane-quad launch on the z-convolved copy each build their
                               tile's staging plan instead of sharing one per tile (same results) */
-    VT_ACCUMULATE = 262144,/* vt_volume_place only: the sums start from `out` as found instead of +0; voxels of tiles no copy can reach
-                              are neither read nor written */
+    VT_ACCUMULATE = 262144,/* vt_volume_place and vt_volume_backproject only: the sums start from `out` as found instead of +0; voxels of
+                              tiles no copy (no image) can reach are neither read nor written */
     VT_PLACE_DENSE = 524288/* vt_volume_place only, diagnostic: every matrix is listed for every output tile (same results) */
 };
 
@@ -79,8 +79,12 @@ enum vt_create_flags {
     VT_EDGE_SCIPY = 16,      /* boundary contract of the reference's CPU path (scipy.ndimage.affine_transform, mode='constant', cval=0,
                                 transforms.py:147-152) instead of the GPU path's texture contract: hard cut-off outside [0, dim-1],
                                 mirrored taps inside, mirror-boundary prefilter.  Whole-volume handles only.                 */
-    VT_SRC_DEFERRED = 8      /* `data` may be NULL: the resident window starts zero-filled, is filled plane range by plane
+    VT_SRC_DEFERRED = 8,     /* `data` may be NULL: the resident window starts zero-filled, is filled plane range by plane
                                 range with vt_volume_upload_planes and becomes usable with vt_volume_finalize              */
+    VT_STACK = 32            /* the planes are independent images (a tilt series) for vt_volume_backproject: filt_* interpolations prefilter
+                                along axes 2 and 1 only, and such a handle (in-plane coefficients) refuses every other sampling entry
+                                point with VT_EUNSUPPORTED.  With the other interpolations the flag changes nothing.  Not together with
+                                VT_EDGE_SCIPY, a slab window or VT_SRC_DEFERRED (VT_EUNSUPPORTED).                          */
 };
 
 enum vt_error {
@@ -98,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -343,6 +347,37 @@ int vt_volume_place(vt_volume_t* vol, int n, const float* m4x4s, const double* w
                     int out_d, int out_h, int out_w, float* out, int flags);
 int vt_volume_place_f64(vt_volume_t* vol, int n, const double* m4x4s, const double* weights /* n, or NULL = all 1 */,
                         int out_d, int out_h, int out_w, float* out, int flags);
+
+/* ---- back-projection: a stack of images (a tilt series) summed into one volume, the transpose of vt_volume_project_batch: weighted
+ * back-projection of a filtered series, the second half of a SIRT step, sub-tomograms straight from a resident series.  The handle holds
+ * the stack S as its (depth, height, width) = (T, H, W).  m4x4s: n x 16 pull matrices, output voxel index -> image coordinate,
+ * y = M_i[1,:3] . (d,h,w) + M_i[1,3], x = M_i[2,:3] . (d,h,w) + M_i[2,3]; rows 0 and 3 are ignored.  planes: n image indices inside [0, T),
+ * or NULL for planes[i] = i (then n must equal T).  out: out_depth * out_height * out_width float32 (host, or device with VT_OUT_DEVICE):
+ *     out[v] = float32(b[v] + w_0 * B_0[v] + w_1 * B_1[v] + ...)        ascending i
+ * with B_i[v] the float32 value of the handle's interpolation taken in TWO dimensions in image planes[i] at (y, x): bilinear, or the 4 x 4
+ * cubic B-spline with the weights of the handle's 3-D kind; taps outside the image read 0; B_i[v] counts only where -0.5 <= y < H - 0.5 and
+ * -0.5 <= x < W - 0.5, evaluated by the float64 fma chain of every other entry point.  weights: n float64, or NULL for all 1.  Each term is
+ * widened to float64, multiplied by its weight and added by vt_volume_place's accumulation step; the sum is rounded to float32 once.  b[v]
+ * is +0, or with VT_ACCUMULATE double(out[v]) as found.  Repeated calls give identical bits.
+ * filt_* interpolations need coefficients that were prefiltered in-plane only: a handle created with VT_STACK; without it the call is
+ * refused with VT_EUNSUPPORTED, as it is on VT_EDGE_SCIPY handles.
+ * ONE workgroup per output tile (vt_volume_place's tile for that output shape; last_kernel 18, last_grid = output tiles) walks all n
+ * entries, skips those whose tile maps outside the image, stages ONE image patch per entry into one of two LDS buffers -- the next
+ * entry's patch is in flight while the current one is sampled -- and adds; no lists, no memset, no atomics.  With VT_ACCUMULATE a tile no
+ * entry reaches is neither read nor written.  Identity: with a linear handle, vt_volume_place with the matrices whose row 0 is
+ * (0, 0, 0, planes[i]) writes the same bits (up to the sign of a zero sample), with twice the staged bytes and taps.
+ * last_tile = the tile, last_lds_dims = (2, Ly, Lx) of the largest staged patch, last_lds_bytes = the launch's allocation (two buffers).
+ * Entries of which two patches do not fit the LDS gather from global memory inside the same launch; VT_FORCE_DIRECT makes every entry do
+ * so, VT_FORCE_TILED selects the default.  Every other flag is ignored.  Device memory beyond the source: n x 200 bytes of tables.
+ * Host `out`: returns after the copy back (with VT_ACCUMULATE the caller's array is uploaded first); VT_OUT_DEVICE: asynchronous on the
+ * handle's stream.  Slab handles and handles not yet finalized: VT_EINVAL; n <= 0, non-positive dims, non-finite matrix entries or
+ * weights, a plane index outside [0, T), planes == NULL with n != T: VT_EINVAL. */
+int vt_volume_backproject(vt_volume_t* vol, int n, const float* m4x4s, const int32_t* planes /* n, or NULL */,
+                          const double* weights /* n, or NULL = all 1 */, int out_depth, int out_height, int out_width,
+                          float* out, int flags);
+int vt_volume_backproject_f64(vt_volume_t* vol, int n, const double* m4x4s, const int32_t* planes /* n, or NULL */,
+                              const double* weights /* n, or NULL = all 1 */, int out_depth, int out_height, int out_width,
+                              float* out, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

@@ -19,7 +19,7 @@ INTERP_CODES = {'linear': 0, 'bspline': 1, 'bspline_simple': 2, 'filt_bspline': 
 # enum vt_flags
 OUT_DEVICE, KEEP_OUTSIDE, FORCE_DIRECT, FORCE_TILED, NO_ZSEP, NO_MARCH, NO_ZPAIR, NO_PACKED, FORCE_PACKED, FORCE_XSWAP, NO_RSWAP, NO_QUAD, ONESHOT_EDGE_SCIPY, NO_BLOCK, NO_ZFIR, NO_REORIENT, NO_ROWS, NO_PLANSHARE, ACCUMULATE, PLACE_DENSE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536, 131072, 262144, 524288
 # enum vt_create_flags
-SRC_DEVICE, SLAB_LO_INTERIOR, SLAB_HI_INTERIOR, SRC_DEFERRED, EDGE_SCIPY = 1, 2, 4, 8, 16
+SRC_DEVICE, SLAB_LO_INTERIOR, SLAB_HI_INTERIOR, SRC_DEFERRED, EDGE_SCIPY, STACK = 1, 2, 4, 8, 16, 32
 
 # every symbol include/voltools_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -35,7 +35,7 @@ SYMBOLS = [
     'vt_volume_extract_sum', 'vt_volume_extract_sum_f64', 'vt_volume_extract_dot', 'vt_volume_extract_dot_f64',
     'vt_volume_extract_dot_multi', 'vt_volume_extract_dot_multi_f64',
     'vt_volume_extract_sum_multi', 'vt_volume_extract_sum_multi_f64',
-    'vt_volume_place', 'vt_volume_place_f64',
+    'vt_volume_place', 'vt_volume_place_f64', 'vt_volume_backproject', 'vt_volume_backproject_f64',
 ]
 
 
@@ -129,6 +129,8 @@ def load():
     L.vt_volume_extract_sum_multi_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_place.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_place_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_backproject.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_backproject_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_batch_f64.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_project_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int]

@@ -277,6 +277,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractdotmulti_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractsummulti_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_place_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_backproject_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -504,8 +505,10 @@ struct PinnedScope {
 };
 
 // Run the three passes X, Y, Z (reference order, transforms.py:305-307) on d_a, using d_b as the
-// ping-pong partner.  Returns which buffer holds the coefficients.
-int run_prefilter(float* d_a, float* d_b, int D, int H, int W, int P, bool lo_interior_axis0, hipStream_t st, float** result)
+// ping-pong partner.  Returns which buffer holds the coefficients.  in_plane_only (VT_STACK handles): the planes are independent
+// images, the axis-0 pass does not run.
+int run_prefilter(float* d_a, float* d_b, int D, int H, int W, int P, bool lo_interior_axis0, hipStream_t st, float** result,
+                  bool in_plane_only = false)
 {
     float* cur = d_a;
     float* oth = d_b;
@@ -517,7 +520,7 @@ int run_prefilter(float* d_a, float* d_b, int D, int H, int W, int P, bool lo_in
         float* t = cur; cur = oth; oth = t;
         first_pass = 2;
     }
-    for (int i = first_pass; i < 3; ++i) {
+    for (int i = first_pass; i < (in_plane_only ? 2 : 3); ++i) {
         const int axis = order[i];
         const bool interior = (axis == 0) && lo_interior_axis0;
         if (prefilter_axis_in_place_ok(axis, D, H, W)) {
@@ -1038,9 +1041,19 @@ int host_output_buffer(vt_volume* v, size_t n_elems, float** d_out)
     return 0;
 }
 
+// A VT_STACK handle with a filt_* interpolation holds coefficients that were prefiltered inside each plane only: every entry point that
+// samples in three dimensions refuses it (vt_volume_backproject is the one that reads them).
+int refuse_in_plane(const vt_volume* v)
+{
+    if (v->stack && is_filtered(v->interp))
+        return fail(VT_EUNSUPPORTED, "the handle's coefficients are in-plane (VT_STACK with a filt_* interpolation): only vt_volume_backproject samples them");
+    return 0;
+}
+
 int do_affine(vt_volume* v, const double m4x4[16], float* out, int flags)
 {
     if (!v || !m4x4 || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (v->deferred) return fail(VT_EINVAL, "handle was created with VT_SRC_DEFERRED and has not been finalized (vt_volume_finalize)");
     int rc = use_device(v->dev);
     if (rc) return rc;
@@ -1127,7 +1140,7 @@ int finalize_resident(vt_volume* v, bool lo_interior)
         }
         float* res = nullptr;
         hipEventRecord(v->ev0, v->stream);
-        int rc = run_prefilter(v->d_src, d_tmp, v->D, v->H, v->W, v->P, lo_interior, v->stream, &res);
+        int rc = run_prefilter(v->d_src, d_tmp, v->D, v->H, v->W, v->P, lo_interior, v->stream, &res, v->stack);
         hipEventRecord(v->ev1, v->stream);
         hipError_t es = hipStreamSynchronize(v->stream);
         if (rc || es != hipSuccess) {
@@ -1157,6 +1170,11 @@ int create_common(int dev, int D, int H, int W, int interp, const float* data, i
     if ((int64_t)D * H > 0x7fffffffLL || (int64_t)H * W > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "plane count/size exceeds 2^31");
     if (gD <= 0 || plane0 + D < 0 || plane0 > gD) return fail(VT_EINVAL, "slab window [%lld,%lld) outside global depth %lld",
                                                                (long long)plane0, (long long)(plane0 + D), (long long)gD);
+    if (cflags & VT_STACK) {
+        if (cflags & VT_EDGE_SCIPY) return fail(VT_EUNSUPPORTED, "VT_STACK cannot be combined with VT_EDGE_SCIPY");
+        if (plane0 != 0 || gD != D || out_plane0 != 0 || oD != D) return fail(VT_EUNSUPPORTED, "VT_STACK is available for whole-volume handles only (no slab window)");
+        if (cflags & VT_SRC_DEFERRED) return fail(VT_EUNSUPPORTED, "VT_STACK cannot be combined with deferred construction (VT_SRC_DEFERRED)");
+    }
     int rc = init_device(dev);
     if (rc) return rc;
 
@@ -1179,6 +1197,7 @@ int create_common(int dev, int D, int H, int W, int interp, const float* data, i
     v->oD = oD; v->oH = uH; v->oW = uW;
     v->plane0 = plane0; v->gD = gD; v->out_plane0 = out_plane0;
     v->edge_pad = pad;
+    v->stack = (cflags & VT_STACK) != 0;
     v->tune.read();
     if (v->tune.max_resident_gb > 0.0) v->lazy.max_resident = (uint64_t)(v->tune.max_resident_gb * 1073741824.0);
 
@@ -1465,6 +1484,7 @@ int oneshot_pipelined(int dev, const float* h_volume, int D, int H, int W, int i
 int do_affine_batch(vt_volume* v, int n, const double* m4x4s, float* out, int flags)
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
     int rc = use_device(v->dev);
@@ -1550,6 +1570,7 @@ bool extract_routes_tiled(int interp, int bd, int bh, int bw)
 int do_extract(vt_volume* v, int n, const double* m4x4s, int bd, int bh, int bw, float* out, int flags)
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
     if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
     if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
@@ -1655,6 +1676,7 @@ int do_extract(vt_volume* v, int n, const double* m4x4s, int bd, int bh, int bw,
 int do_project(vt_volume* v, const double m4x4[16], float* out, int flags)
 {
     if (!v || !m4x4 || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
     int rc = use_device(v->dev);
     if (rc) return rc;
@@ -1781,6 +1803,7 @@ bool project_batch_routes_fused(int interp, int depth, int height, int width)
 int do_project_batch(vt_volume* v, int n, const double* m4x4s, int depth, int height, int width, float* out, int flags)
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
     if (depth <= 0 || height <= 0 || width <= 0) return fail(VT_EINVAL, "non-positive output dims (%d,%d,%d)", depth, height, width);
     if ((int64_t)depth * height > 0x7fffffffLL || (int64_t)height * width > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
@@ -1899,6 +1922,7 @@ int do_project_batch(vt_volume* v, int n, const double* m4x4s, int depth, int he
 int do_extract_sum(vt_volume* v, int n, const double* m4x4s, const double* weights, int bd, int bh, int bw, float* out, int flags)
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
     if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
     if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
@@ -1995,6 +2019,7 @@ int do_extract_sum(vt_volume* v, int n, const double* m4x4s, const double* weigh
 int do_extract_dot(vt_volume* v, int n, const double* m4x4s, const float* tmpl, const float* mask, int bd, int bh, int bw, double* out, int flags)
 {
     if (!v || !m4x4s || !tmpl || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
     if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
     if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
@@ -2108,6 +2133,7 @@ int do_extract_dot_multi(vt_volume* v, int n, const double* m4x4s, int k, const 
                          double* out, int flags)
 {
     if (!v || !m4x4s || !tmpls || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
     if (k <= 0) return fail(VT_EINVAL, "template count %d", k);
     if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
@@ -2232,6 +2258,7 @@ int do_extract_dot_multi(vt_volume* v, int n, const double* m4x4s, int k, const 
 int do_extract_sum_multi(vt_volume* v, int n, const double* m4x4s, int g, const double* weights, int bd, int bh, int bw, float* out, int flags)
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
     if (g <= 0) return fail(VT_EINVAL, "column count %d", g);
     if (!weights) return fail(VT_EINVAL, "NULL weights");
@@ -2394,6 +2421,7 @@ void place_tile_range(const ExtractEntry& e, const AffineParams& p, const int T[
 int do_place(vt_volume* v, int n, const double* m4x4s, const double* weights, int od, int oh, int ow, float* out, int flags)
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
     if (od <= 0 || oh <= 0 || ow <= 0) return fail(VT_EINVAL, "non-positive output dims (%d,%d,%d)", od, oh, ow);
     if ((int64_t)od * oh > 0x7fffffffLL || (int64_t)oh * ow > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
@@ -2527,6 +2555,112 @@ int do_place(vt_volume* v, int n, const double* m4x4s, const double* weights, in
                             v->d_batch_m + per * (size_t)n, d_ids, d_ids + n_tiles, d_ids + 2 * n_tiles + 1, (int)n_tiles, accumulate, p,
                             (int)lds_bytes, v->stream));
     }
+    if (host_out) {
+        VT_HIP(pin.copy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+        VT_HIP(hipStreamSynchronize(v->stream));
+    }
+    return 0;
+}
+
+// One volume of shape (od, oh, ow) from the handle's planes taken as a stack of T images: n weighted 2-D samples per voxel, image
+// planes[i] at rows 1 and 2 of matrix i, summed in float64 in ascending order and rounded once -- do_place without the lists: kernel 18
+// (vt_kernels_backproject.hip) runs one workgroup per output tile over all n entries, so nothing is zeroed first.  The tile is do_place's,
+// the entries are do_place's for the matrix whose row 0 is (0, 0, 0, planes[i]); an entry stages into LDS when two patches of its size
+// fit (the kernel keeps the next entry's patch in flight while it samples).  Does not read or change the handle's own output shape.
+int do_backproject(vt_volume* v, int n, const double* m4x4s, const int32_t* planes, const double* weights, int od, int oh, int ow, float* out,
+                   int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    if (od <= 0 || oh <= 0 || ow <= 0) return fail(VT_EINVAL, "non-positive output dims (%d,%d,%d)", od, oh, ow);
+    if ((int64_t)od * oh > 0x7fffffffLL || (int64_t)oh * ow > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
+    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
+    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
+        return fail(VT_EINVAL, "back-projection is available for whole-volume handles only (this one holds a slab window)");
+    if (is_filtered(v->interp) && !v->stack)
+        return fail(VT_EUNSUPPORTED, "the handle's coefficients are prefiltered along axis 0 as well: back-projection with a filt_* interpolation "
+                                     "needs in-plane coefficients (create the handle with VT_STACK)");
+    if (v->edge_pad) return fail(VT_EUNSUPPORTED, "back-projection is not available on VT_EDGE_SCIPY handles");
+    int rc = use_device(v->dev);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    for (size_t i = 0; i < (size_t)n * 16; ++i)
+        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    if (weights)
+        for (int i = 0; i < n; ++i)
+            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %d is not finite", i);
+    if (planes) {
+        for (int i = 0; i < n; ++i)
+            if (planes[i] < 0 || planes[i] >= v->D) return fail(VT_EINVAL, "plane index %d of entry %d outside [0, %d)", planes[i], i, v->D);
+    } else if (n != v->D) {
+        return fail(VT_EINVAL, "%d matrices for a stack of %d images and no plane indices", n, v->D);
+    }
+
+    const bool cubic = is_cubic(v->interp);
+    const int shape[3] = {od, oh, ow};
+    const size_t n_out = (size_t)od * oh * ow;
+    const bool host_out = !(flags & VT_OUT_DEVICE);
+    const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
+    const bool accumulate = (flags & VT_ACCUMULATE) != 0;
+    const int cfg = extract_pick_tile(cubic, shape, nullptr);      // a function of (output shape, interpolation): do_place's tile
+    int T[3];
+    extract_tile(cfg, &T[0], &T[1], &T[2]);
+    const int nT[3] = {(od + T[0] - 1) / T[0], (oh + T[1] - 1) / T[1], (ow + T[2] - 1) / T[2]};
+    const int64_t tiles = (int64_t)nT[0] * nT[1] * nT[2];
+    if (tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large (%lld tiles)", (long long)tiles);
+
+    // the launch's tables: one ExtractEntry per matrix, then the n weights
+    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
+    const size_t per = sizeof(ExtractEntry) / sizeof(double);
+    std::vector<double>& tab = v->h_batch_m;
+    tab.resize((size_t)n * (per + 1));
+    int Lmax[2] = {0, 0};
+    int64_t buf_floats = 4;
+    for (int i = 0; i < n; ++i) {
+        const double* a = m4x4s + 16 * (size_t)i;
+        double m[12] = {0, 0, 0, (double)(planes ? planes[i] : i), a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11]};
+        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
+        // tile reach, Q32.32 increments and patch dims by extract_box_dims' rule (no cap: the cap below is on two 2-D patches)
+        extract_fill_entry(m, cfg, cubic, 0x7fffffff, false, e);
+        const int64_t patch = (int64_t)e->Ly * e->Lx;
+        if (e->tiled && !force_direct && 2 * patch * 4 <= (int64_t)v->lds_limit) {
+            if (patch > buf_floats || Lmax[0] == 0) { Lmax[0] = e->Ly; Lmax[1] = e->Lx; }      // the largest staged patch
+            buf_floats = std::max(buf_floats, patch);
+        } else {
+            e->tiled = 0;
+        }
+        tab[per * (size_t)n + (size_t)i] = weights ? weights[i] : 1.0;
+    }
+    const int lds_bytes = (int)(2 * buf_floats * 4);
+    AffineParams p;
+    std::memset(&p, 0, sizeof(p));
+    TilePlan plan;
+    {
+        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, od, oh, ow, true);
+        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, output dims, valid interval
+    }
+    p.nTd = nT[0]; p.nTh = nT[1]; p.nTw = nT[2];
+
+    v->last_kernel = 18;
+    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
+    v->last_lds[0] = 2; v->last_lds[1] = Lmax[0]; v->last_lds[2] = Lmax[1];
+    v->last_lds_bytes = lds_bytes; v->last_grid = (int)tiles;
+
+    float* d_out = out;
+    PinnedScope pin(host_out ? out : nullptr, host_out ? n_out * sizeof(float) : 0);       // the caller's array: in (accumulate) and out
+    if (host_out) {
+        if ((rc = host_output_buffer(v, n_out, &d_out))) return rc;
+        if (accumulate) VT_HIP(pin.copy(d_out, out, n_out * sizeof(float), hipMemcpyHostToDevice, v->stream));
+    }
+    if (v->batch_m_cap < tab.size()) {
+        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
+        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
+        v->batch_m_cap = tab.size();
+    }
+    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
+                               hipMemcpyHostToDevice, v->stream));
+    VT_HIP(launch_backproject(cfg, v->interp, v->d_src, d_out, v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m),
+                              v->d_batch_m + per * (size_t)n, n, (int)buf_floats, accumulate, p, lds_bytes, v->stream));
     if (host_out) {
         VT_HIP(pin.copy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, v->stream));
         VT_HIP(hipStreamSynchronize(v->stream));
@@ -2684,7 +2818,7 @@ int vt_host_unregister(int dev, void* ptr)
 int vt_volume_create(int dev, int depth, int height, int width, int interp, const float* data,
                      int create_flags, vt_volume_t** out)
 {
-    return create_common(dev, depth, height, width, interp, data, create_flags & (VT_SRC_DEVICE | VT_EDGE_SCIPY),
+    return create_common(dev, depth, height, width, interp, data, create_flags & (VT_SRC_DEVICE | VT_EDGE_SCIPY | VT_STACK),
                          0, depth, 0, depth, out);
 }
 
@@ -2922,6 +3056,22 @@ int vt_volume_place_f64(vt_volume_t* v, int n, const double* m4x4s, const double
                         int flags)
 {
     return do_place(v, n, m4x4s, weights, out_d, out_h, out_w, out, flags);
+}
+
+int vt_volume_backproject(vt_volume_t* v, int n, const float* m4x4s, const int32_t* planes, const double* weights, int out_d, int out_h,
+                          int out_w, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    std::vector<double> m((size_t)n * 16);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
+    return do_backproject(v, n, m.data(), planes, weights, out_d, out_h, out_w, out, flags);
+}
+
+int vt_volume_backproject_f64(vt_volume_t* v, int n, const double* m4x4s, const int32_t* planes, const double* weights, int out_d, int out_h,
+                              int out_w, float* out, int flags)
+{
+    return do_backproject(v, n, m4x4s, planes, weights, out_d, out_h, out_w, out, flags);
 }
 
 int vt_volume_extract_dot(vt_volume_t* v, int n, const float* m4x4s, const float* tmpl, const float* mask, int box_d, int box_h, int box_w,

@@ -150,6 +150,7 @@ struct vt_volume {
     int proj_sum_oD = 0;
     int64_t proj_sum_oplane0 = 0;
     int edge_pad = 0;                  // VT_EDGE_SCIPY: the resident copy carries this many mirrored voxels on every side (0 = texture contract)
+    bool stack = false;                // VT_STACK: the planes are independent images; filt_* coefficients are prefiltered in-plane only
     bool owns_stream = true;
     bool deferred = false;             // created with VT_SRC_DEFERRED: planes still being uploaded, not usable before vt_volume_finalize
     bool lo_interior = false;          // ... and its VT_SLAB_LO_INTERIOR flag, kept for the prefilter at finalize

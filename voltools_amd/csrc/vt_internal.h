@@ -339,6 +339,15 @@ hipError_t launch_place(int cfg, int interp, const float* src, float* out, const
                         const double* d_wts, const int* d_tile_ids, const int* d_offs, const int* d_idx, int n_tiles, bool accumulate,
                         const AffineParams& p, int lds_bytes, hipStream_t stream);
 
+// a stack of images back-projected into one volume (vt_kernels_backproject.hip, kind 18): launch_place's tile and entries, rows 1 and 2 of
+// an entry's matrix map an output voxel into image (int)m[3] of the stack; one workgroup per output tile walks all n entries.  Two LDS
+// buffers of buf_floats floats each (lds_bytes >= 8 * buf_floats, every tiled entry's Ly * Lx <= buf_floats); Lz is not read.
+// accumulate: sums start from `out` as found, tiles no entry reaches are not written; otherwise every voxel is written.
+hipError_t init_backproject_kernels();
+hipError_t launch_backproject(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
+                              const double* d_wts, int n, int buf_floats, bool accumulate, const AffineParams& p, int lds_bytes,
+                              hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

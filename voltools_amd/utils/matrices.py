@@ -205,6 +205,33 @@ def tilt_matrices(angles, tilt_axis: int = 1, shape=None, rotation_units: str = 
     return np.stack(ms)
 
 
+def backproject_matrices(angles, tilt_axis: int = 1, output_shape=None, image_shape=None, rotation_units: str = 'deg',
+                         center: Vec3 = None) -> np.ndarray:
+    """Pull matrices (n, 4, 4), float64, that back-project a tilt series into a volume of shape ``output_shape``
+    (``StaticVolume.backproject``): the inverses of ``tilt_matrices(angles, tilt_axis, output_shape, rotation_units, center)``, so rows
+    1 and 2 of matrix ``i`` send a voxel index of the volume to the pixel of image ``i`` that ``tilt_series`` of that volume sums it into.
+
+    ``image_shape`` (``(H, W)``, or ``(T, H, W)`` whose last two count): the images' own shape where it differs from
+    ``output_shape[1:]``; ``(image_shape - 1) / 2 - (output_shape[1:] - 1) / 2`` is added to the translations of rows 1 and 2, which
+    puts the centre of the volume's projection at the centre of the image.
+    """
+    out = _box_shape(output_shape)
+    fwd = np.asarray(tilt_matrices(angles, tilt_axis, out, rotation_units, center), dtype=np.float64)
+    ms = np.linalg.inv(fwd)
+    ms[:, 3, :] = (0.0, 0.0, 0.0, 1.0)
+    if image_shape is not None:
+        try:
+            img = tuple(image_shape)
+        except TypeError:
+            raise ValueError('image_shape must be (H, W) or (T, H, W), positive ints')
+        if len(img) not in (2, 3) or not all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) and b > 0 for b in img):
+            raise ValueError('image_shape must be (H, W) or (T, H, W), positive ints')
+        shift = (np.asarray(img[-2:], dtype=np.float64) - 1.0) / 2.0 - (np.asarray(out[1:], dtype=np.float64) - 1.0) / 2.0
+        ms[:, 1, 3] += shift[0]
+        ms[:, 2, 3] += shift[1]
+    return ms
+
+
 def _box_shape(box_shape) -> Tuple[int, int, int]:
     """Three positive ints, or ValueError."""
     try:

@@ -10,11 +10,12 @@ import time
 from typing import Tuple, Union
 
 import numpy as np
-from scipy.ndimage import affine_transform, spline_filter
+from scipy.ndimage import affine_transform, map_coordinates, spline_filter
 
 from . import _native
 from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
 from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, place_matrices, tilt_matrices,
+                    backproject_matrices,
                     get_available_devices, switch_to_device)
 from .utils.matrices import _box_shape
 
@@ -24,18 +25,27 @@ Vec3 = Union[Tuple[float, float, float], np.ndarray]
 class StaticVolume:
     """For StaticVolume transforms the boolean reshape cannot be given as an argument."""
 
-    def __init__(self, data, interpolation: str = 'linear', device: str = 'gpu', *, edge: str = 'texture', max_resident_bytes: int = 0):
+    def __init__(self, data, interpolation: str = 'linear', device: str = 'gpu', *, edge: str = 'texture', max_resident_bytes: int = 0,
+                 stack: bool = False):
         """``edge`` (extension, GPU devices): ``'texture'`` = the reference GPU path's boundary contract, ``'scipy'`` = the
         contract of its CPU path (see ``transforms.py`` of this package).  ``max_resident_bytes`` (extension, GPU devices): how much HBM
         this volume may keep resident, its plain copy included -- the copies built lazily per orientation used (``info().resident_bytes``)
         are released least recently used first to stay inside it, and a copy that cannot fit is not built (the call then runs on the
         kernels that sample the plain layout; results are the same).  0 = no limit (or the ``VT_MAX_RESIDENT_GB`` environment default).
-        The reference keeps one CUDA array per StaticVolume (``volume.py:37-45``)."""
+        The reference keeps one CUDA array per StaticVolume (``volume.py:37-45``).  ``stack`` (extension): the planes are independent
+        images, a tilt series for ``backproject``; ``filt_*`` interpolations then prefilter inside each plane only (``spline_filter`` per
+        plane on ``device='cpu'``), and such a volume serves ``backproject`` / ``backproject_tilts`` alone.  With the other interpolations
+        the flag changes nothing.  Not together with ``edge='scipy'``."""
         if data.ndim != 3:
             raise ValueError('Expected a 3D array')
         if edge not in ('texture', 'scipy'):
             raise ValueError("edge must be 'texture' or 'scipy'")
+        if not isinstance(stack, (bool, np.bool_)):
+            raise ValueError('stack must be a bool')
+        if stack and edge == 'scipy':
+            raise ValueError("stack=True cannot be combined with edge='scipy'")
         self.edge = edge
+        self.stack = bool(stack)
         if device not in get_available_devices():
             raise ValueError(f'Unknown device ({device}), must be one of {get_available_devices()}')
 
@@ -58,6 +68,8 @@ class StaticVolume:
                 ptr, flags = host.ctypes.data, 0
             if edge == 'scipy':
                 flags |= _native.EDGE_SCIPY
+            if self.stack:
+                flags |= _native.STACK
             h = ctypes.c_void_p()
             _native.check(self._lib.vt_volume_create(self._dev, *self.shape, _INTERPOLATIONS[interpolation],
                                                      ptr, flags, ctypes.byref(h)), 'vt_volume_create')
@@ -800,6 +812,102 @@ class StaticVolume:
         ``utils.tilt_matrices``.  ``tilt_series([a], k)[0]`` is the image of ``project(rotation=r, rotation_order='sxyz')`` with
         ``r[k] = a``."""
         return self.projection_batch(tilt_matrices(angles, tilt_axis, self.shape, rotation_units, center), output_shape, profile, output)
+
+    # -- back-projection: a stack of images summed into one volume (extension: the transpose of projection_batch; WBP, SIRT) ----
+    def backproject(self, matrices: np.ndarray, output_shape, weights=None, profile: bool = False, output=None, *,
+                    planes=None, accumulate: bool = False, _flags: int = 0) -> Union[np.ndarray, None]:
+        """This volume taken as a stack of ``T`` images ``(T, H, W)`` and back-projected into one volume of shape ``output_shape =
+        (oD, oH, oW)``: ``out = float32(b + sum_i weights[i] * B_i)`` with ``B_i[d, h, w]`` image ``planes[i]`` interpolated in two
+        dimensions at ``y = M_i[1, :3] . (d, h, w) + M_i[1, 3]``, ``x = M_i[2, :3] . (d, h, w) + M_i[2, 3]`` (rows 0 and 3 of a matrix are
+        ignored; ``utils.backproject_matrices`` builds the matrices of a tilt series), 0 outside the image, and ``b`` zero, or with
+        ``accumulate=True`` the contents of ``output``, which is then required.  The interpolation is the volume's, in the plane: bilinear,
+        or the 4 x 4 cubic B-spline; ``filt_*`` needs a volume built with ``stack=True``.  Every term is widened to float64, multiplied by
+        its float64 weight and added in float64, in the order of ``matrices``; the sum is rounded to float32 once.
+        ``planes``: ``n`` image indices inside ``[0, T)``; None = ``0 .. n-1``, and then ``n`` must equal ``T``.  ``weights``: shape
+        ``(n,)``, converted to float64; None = ones.  Returns a float32 array ``(oD, oH, oW)``, or fills ``output`` of that shape (numpy,
+        ``vt.empty`` device array, torch-ROCm tensor) and returns None on a GPU device, like ``place``.  Repeated calls give identical
+        bits.  float64 matrices keep their precision; anything else is taken as float32."""
+        shape = _box_shape(output_shape)
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] != (4, 4) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        n = ms.shape[0]
+        w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f'weights must have shape ({n},)')
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        if planes is None:
+            if n != self.shape[0]:
+                raise ValueError(f'{n} matrices for a stack of {self.shape[0]} images: planes must be given')
+            pl = None
+        else:
+            pl = np.asarray(planes)
+            if pl.shape != (n,) or not np.issubdtype(pl.dtype, np.integer):
+                raise ValueError(f'planes must be {n} integers')
+            if pl.min() < 0 or pl.max() >= self.shape[0]:
+                raise ValueError(f'planes must lie inside [0, {self.shape[0]})')
+            pl = np.ascontiguousarray(pl, dtype=np.int32)
+        if accumulate and output is None:
+            raise ValueError('accumulate=True adds into output, which must be given')
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.interpolation.startswith('filt_') and not self.stack:
+            raise ValueError('back-projection with a filt_* interpolation needs in-plane coefficients: build the volume with stack=True')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            acc = np.asarray(output).astype(np.float64) if accumulate else np.zeros(shape, dtype=np.float64)
+            d, h, x = np.meshgrid(*(np.arange(s, dtype=np.float64) for s in shape), indexing='ij')
+            coeffs = {}
+            t_start = time.time()
+            for i in range(n):
+                k = i if pl is None else int(pl[i])
+                if k not in coeffs:     # spline_filter per plane: the planes are independent images
+                    img = np.asarray(self.data[k], dtype=np.float64)
+                    coeffs[k] = spline_filter(img, order, output=np.float64, mode='constant') if prefilter else img
+                m = ms[i].astype(np.float64)
+                yy = m[1, 0] * d + m[1, 1] * h + m[1, 2] * x + m[1, 3]
+                xx = m[2, 0] * d + m[2, 1] * h + m[2, 2] * x + m[2, 3]
+                one = map_coordinates(coeffs[k], [yy, xx], order=order, mode='constant', cval=0.0, prefilter=False, output=np.float64)
+                acc += w[i] * one.astype(np.float32).astype(np.float64)
+            res = acc.astype(np.float32)
+            if profile:
+                print(f'{n} images back-projected in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags | (_native.ACCUMULATE if accumulate else 0)
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        pl_ptr = None if pl is None else pl.ctypes.data
+        if ms.dtype == np.float64:
+            rc = self._lib.vt_volume_backproject_f64(self._handle, n, ms.ctypes.data, pl_ptr, w.ctypes.data, *shape, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_backproject(self._handle, n, ms.ctypes.data, pl_ptr, w.ctypes.data, *shape, ptr, flags)
+        _native.check(rc, 'vt_volume_backproject')
+        if profile:
+            print(f'{n} images back-projected in {self.timer_stop():.3f}ms')
+        return result
+
+    def backproject_tilts(self, angles, tilt_axis: int = 1, rotation_units: str = 'deg', center: Vec3 = None, output_shape=None,
+                          weights=None, profile: bool = False, output=None, *, accumulate: bool = False) -> Union[np.ndarray, None]:
+        """``backproject`` of this stack as the tilt series ``tilt_series(angles, tilt_axis, ...)`` of a volume of shape ``output_shape``
+        (required) would give: image ``i`` belongs to ``angles[i]``; the matrices of ``utils.backproject_matrices`` for this stack's image
+        shape, in float64."""
+        if output_shape is None:
+            raise ValueError('output_shape is required')
+        ms = backproject_matrices(angles, tilt_axis, output_shape, self.shape[1:], rotation_units, center)
+        return self.backproject(ms, output_shape, weights, profile, output, accumulate=accumulate)
 
     def translate(self, translation: Vec3, profile: bool = False, output=None):
         return self.affine(translation_matrix(translation), profile, output)
