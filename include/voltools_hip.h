@@ -66,8 +66,8 @@ enum vt_flags {
     VT_NO_ROWS = 65536,    /* diagnostic: maps that leave axis 2 alone take the axis-exchange path, not the row kernel (kind 10) */
     VT_NO_PLANSHARE = 131072,/* diagnostic: the chunk layers of a cubic plane-quad launch on the z-convolved copy each build their
                               tile's staging plan instead of sharing one per tile (same results) */
-    VT_ACCUMULATE = 262144,/* vt_volume_place and vt_volume_backproject only: the sums start from `out` as found instead of +0; voxels of
-                              tiles no copy (no image) can reach are neither read nor written */
+    VT_ACCUMULATE = 262144,/* vt_volume_place and vt_volume_backproject only (vt_volume_backproject_boxes: per box): the sums start from
+                              `out` as found instead of +0; voxels of tiles no copy (no image) can reach are neither read nor written */
     VT_PLACE_DENSE = 524288/* vt_volume_place only, diagnostic: every matrix is listed for every output tile (same results) */
 };
 
@@ -102,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -378,6 +378,38 @@ int vt_volume_backproject(vt_volume_t* vol, int n, const float* m4x4s, const int
 int vt_volume_backproject_f64(vt_volume_t* vol, int n, const double* m4x4s, const int32_t* planes /* n, or NULL */,
                               const double* weights /* n, or NULL = all 1 */, int out_depth, int out_height, int out_width,
                               float* out, int flags);
+
+/* ---- nb sub-volumes of one shape back-projected from one resident stack in ONE launch: a box around every particle straight from the
+ * tilt series (per-particle reconstruction of sub-tomogram workflows), the input of vt_volume_extract_dot_multi / _sum_multi.  The handle
+ * holds the stack (T, H, W) as for vt_volume_backproject.  m4x4s: nb x n x 16 pull matrices in C order, entry (b, i) sends a voxel index
+ * INSIDE box b to a pixel of image planes[i]; rows 1 and 2 count, rows 0 and 3 are ignored.  planes: n image indices shared by all boxes,
+ * or NULL for planes[i] = i (then n must equal T).  weights: nb x n float64 in C order, or NULL for all 1.  out: nb consecutive boxes of
+ * box_d * box_h * box_w float32 (host, or device with VT_OUT_DEVICE):
+ *     out[b][v] = float32(base[b][v] + w_{b,0} * B_{b,0}[v] + w_{b,1} * B_{b,1}[v] + ...)        ascending i
+ * with B, the skirt rule, the float64 fma chain, the accumulation step and the single rounding those of vt_volume_backproject, and base =
+ * +0, or with VT_ACCUMULATE double(out[b][v]) as found; a tile that no entry of its box reaches is then neither read nor written.
+ * Bit identity: box b holds exactly what vt_volume_backproject(vol, n, m4x4s + 16 n b, planes, weights + n b, box_d, box_h, box_w, ..,
+ * flags) writes -- on the default route, with VT_FORCE_DIRECT, with VT_ACCUMULATE, and for entries that gather from global memory inside
+ * the staged launch.  A box is therefore a fixed expression of (its matrices and weights, planes, source, box shape, interpolation,
+ * route): it does not depend on nb, on the other boxes, on its place in the batch, on earlier calls or on host versus device output.
+ * ONE workgroup per (box, box tile) (last_kernel 19, last_grid = nb x box tiles, box-major so that the tiles of a box share an XCD's L2)
+ * runs vt_volume_backproject's kernel with a box index.  Whether an entry stages its patch in LDS follows from that entry and the LDS
+ * limit alone, as in vt_volume_backproject; the largest staged patch of the batch only sizes the allocation.  last_tile = the tile
+ * vt_volume_backproject uses for that box shape, last_lds_dims = (2, Ly, Lx) of the largest staged patch, last_lds_bytes = the
+ * allocation.  VT_FORCE_DIRECT / VT_FORCE_TILED as for vt_volume_backproject; every other flag is ignored.  Device memory beyond the
+ * source: nb x n x 200 bytes of tables in a buffer the handle recycles (callers with very many boxes cut the call along the box axis;
+ * the cut cannot show in the result).
+ * Bounds (VT_EUNSUPPORTED beyond): nb x box tiles < 2^31, nb x n < 2^31, a box as for vt_volume_backproject, nb x box bytes within size_t.
+ * Host `out`: returns after the copy back (with VT_ACCUMULATE the caller's array is uploaded first); VT_OUT_DEVICE: asynchronous on the
+ * handle's stream.  Slab handles and handles not yet finalized: VT_EINVAL; filt_* without VT_STACK and VT_EDGE_SCIPY handles:
+ * VT_EUNSUPPORTED; nb <= 0, n <= 0, non-positive box dims, non-finite matrix entries or weights, a plane index outside [0, T), planes ==
+ * NULL with n != T: VT_EINVAL.  A refusal leaves the handle usable. */
+int vt_volume_backproject_boxes(vt_volume_t* vol, int nb, int n, const float* m4x4s /* nb x n x 16 */,
+                                const int32_t* planes /* n, or NULL */, const double* weights /* nb x n, or NULL = all 1 */,
+                                int box_d, int box_h, int box_w, float* out /* nb boxes, C order */, int flags);
+int vt_volume_backproject_boxes_f64(vt_volume_t* vol, int nb, int n, const double* m4x4s /* nb x n x 16 */,
+                                    const int32_t* planes /* n, or NULL */, const double* weights /* nb x n, or NULL = all 1 */,
+                                    int box_d, int box_h, int box_w, float* out /* nb boxes, C order */, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

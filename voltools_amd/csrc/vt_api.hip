@@ -278,6 +278,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_extractsummulti_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_place_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_backproject_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_backproject_boxes_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -2668,6 +2669,123 @@ int do_backproject(vt_volume* v, int n, const double* m4x4s, const int32_t* plan
     return 0;
 }
 
+// nb boxes of one shape (bd, bh, bw) from the handle's stack, n entries per box: box b is what do_backproject writes for matrices
+// m4x4s + 16 n b, the shared planes and weights + n b at that output shape, bit for bit -- the same tile, the same entry through
+// extract_fill_entry, the same per-entry staging decision (two patches of ITS size within lds_limit; the batch-wide largest patch only
+// sizes the allocation and places the second buffer) and kernel 18's text with a box index (kernel 19, vt_kernels_backprojectboxes.hip):
+// one launch of nb x tiles workgroups instead of nb launches, syncs and uploads.  Tables: nb x n entries, then nb x n weights.
+// MT: float or double matrices, widened entry by entry (no nb x n x 16 float64 copy of a float32 batch).
+template <typename MT>
+int do_backproject_boxes(vt_volume* v, int nb, int n, const MT* m4x4s, const int32_t* planes, const double* weights, int bd, int bh,
+                         int bw, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    if (nb <= 0) return fail(VT_EINVAL, "number of boxes %d", nb);
+    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
+    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
+    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
+        return fail(VT_EINVAL, "back-projection is available for whole-volume handles only (this one holds a slab window)");
+    if (is_filtered(v->interp) && !v->stack)
+        return fail(VT_EUNSUPPORTED, "the handle's coefficients are prefiltered along axis 0 as well: back-projection with a filt_* interpolation "
+                                     "needs in-plane coefficients (create the handle with VT_STACK)");
+    if (v->edge_pad) return fail(VT_EUNSUPPORTED, "back-projection is not available on VT_EDGE_SCIPY handles");
+    // the bounds, before anything of the caller's arrays is read
+    const int64_t total = (int64_t)nb * n;                // entries of the call
+    if (total > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "%d boxes x %d entries: more than 2^31 - 1 (box, entry) pairs", nb, n);
+    const bool cubic = is_cubic(v->interp);
+    const int shape[3] = {bd, bh, bw};
+    const size_t box_vox = (size_t)bd * bh * bw;          // < 2^62 by the checks above
+    if (box_vox > (SIZE_MAX / sizeof(float)) / (size_t)nb) return fail(VT_EUNSUPPORTED, "output too large (%d boxes)", nb);
+    const size_t n_out = box_vox * (size_t)nb;
+    const int cfg = extract_pick_tile(cubic, shape, nullptr);      // a function of (box shape, interpolation): do_backproject's tile
+    int T[3];
+    extract_tile(cfg, &T[0], &T[1], &T[2]);
+    const int nT[3] = {(bd + T[0] - 1) / T[0], (bh + T[1] - 1) / T[1], (bw + T[2] - 1) / T[2]};
+    const int64_t tiles = (int64_t)nT[0] * nT[1] * nT[2];
+    if (tiles > 0x7fffffffLL || tiles * nb > 0x7fffffffLL)
+        return fail(VT_EUNSUPPORTED, "grid too large (%d boxes x %lld tiles)", nb, (long long)tiles);
+    int rc = use_device(v->dev);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    for (size_t i = 0; i < (size_t)total * 16; ++i)
+        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    if (weights)
+        for (size_t i = 0; i < (size_t)total; ++i)
+            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %zu is not finite", i);
+    if (planes) {
+        for (int i = 0; i < n; ++i)
+            if (planes[i] < 0 || planes[i] >= v->D) return fail(VT_EINVAL, "plane index %d of entry %d outside [0, %d)", planes[i], i, v->D);
+    } else if (n != v->D) {
+        return fail(VT_EINVAL, "%d matrices per box for a stack of %d images and no plane indices", n, v->D);
+    }
+
+    const bool host_out = !(flags & VT_OUT_DEVICE);
+    const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
+    const bool accumulate = (flags & VT_ACCUMULATE) != 0;
+
+    // the launch's tables: one ExtractEntry per (box, entry), then the nb x n weights; 200 bytes per pair, < 2^31 pairs: no overflow
+    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
+    const size_t per = sizeof(ExtractEntry) / sizeof(double);
+    std::vector<double>& tab = v->h_batch_m;
+    tab.resize((size_t)total * (per + 1));
+    int Lmax[2] = {0, 0};
+    int64_t buf_floats = 4;
+    for (size_t k = 0; k < (size_t)total; ++k) {
+        const MT* a = m4x4s + 16 * k;
+        const int i = (int)(k % (size_t)n);
+        double m[12] = {0, 0, 0, (double)(planes ? planes[i] : i), (double)a[4], (double)a[5], (double)a[6], (double)a[7], (double)a[8],
+                        (double)a[9], (double)a[10], (double)a[11]};
+        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * k);
+        extract_fill_entry(m, cfg, cubic, 0x7fffffff, false, e);      // as in do_backproject
+        const int64_t patch = (int64_t)e->Ly * e->Lx;
+        // staged or not: this entry and lds_limit alone, do_backproject's rule, whatever the rest of the batch holds
+        if (e->tiled && !force_direct && 2 * patch * 4 <= (int64_t)v->lds_limit) {
+            if (patch > buf_floats || Lmax[0] == 0) { Lmax[0] = e->Ly; Lmax[1] = e->Lx; }      // the largest staged patch
+            buf_floats = std::max(buf_floats, patch);
+        } else {
+            e->tiled = 0;
+        }
+        tab[per * (size_t)total + k] = weights ? weights[k] : 1.0;
+    }
+    const int lds_bytes = (int)(2 * buf_floats * 4);
+    AffineParams p;
+    std::memset(&p, 0, sizeof(p));
+    TilePlan plan;
+    {
+        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
+        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
+    }
+    p.nTd = nT[0]; p.nTh = nT[1]; p.nTw = nT[2];
+
+    v->last_kernel = 19;
+    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
+    v->last_lds[0] = 2; v->last_lds[1] = Lmax[0]; v->last_lds[2] = Lmax[1];
+    v->last_lds_bytes = lds_bytes; v->last_grid = (int)(tiles * nb);
+
+    float* d_out = out;
+    PinnedScope pin(host_out ? out : nullptr, host_out ? n_out * sizeof(float) : 0);       // the caller's array: in (accumulate) and out
+    if (host_out) {
+        if ((rc = host_output_buffer(v, n_out, &d_out))) return rc;
+        if (accumulate) VT_HIP(pin.copy(d_out, out, n_out * sizeof(float), hipMemcpyHostToDevice, v->stream));
+    }
+    if (v->batch_m_cap < tab.size()) {
+        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
+        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
+        v->batch_m_cap = tab.size();
+    }
+    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
+                               hipMemcpyHostToDevice, v->stream));
+    VT_HIP(launch_backproject_boxes(cfg, v->interp, v->d_src, d_out, v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m),
+                                    v->d_batch_m + per * (size_t)total, nb, n, (int)buf_floats, accumulate, p, lds_bytes, v->stream));
+    if (host_out) {
+        VT_HIP(pin.copy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, v->stream));
+        VT_HIP(hipStreamSynchronize(v->stream));
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3072,6 +3190,18 @@ int vt_volume_backproject_f64(vt_volume_t* v, int n, const double* m4x4s, const 
                               int out_w, float* out, int flags)
 {
     return do_backproject(v, n, m4x4s, planes, weights, out_d, out_h, out_w, out, flags);
+}
+
+int vt_volume_backproject_boxes(vt_volume_t* v, int nb, int n, const float* m4x4s, const int32_t* planes, const double* weights, int box_d,
+                                int box_h, int box_w, float* out, int flags)
+{
+    return do_backproject_boxes(v, nb, n, m4x4s, planes, weights, box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_backproject_boxes_f64(vt_volume_t* v, int nb, int n, const double* m4x4s, const int32_t* planes, const double* weights,
+                                    int box_d, int box_h, int box_w, float* out, int flags)
+{
+    return do_backproject_boxes(v, nb, n, m4x4s, planes, weights, box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_extract_dot(vt_volume_t* v, int n, const float* m4x4s, const float* tmpl, const float* mask, int box_d, int box_h, int box_w,

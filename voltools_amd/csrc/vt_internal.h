@@ -348,6 +348,14 @@ hipError_t launch_backproject(int cfg, int interp, const float* src, float* out,
                               const double* d_wts, int n, int buf_floats, bool accumulate, const AffineParams& p, int lds_bytes,
                               hipStream_t stream);
 
+// nb boxes of one shape back-projected from one stack in one launch (vt_kernels_backprojectboxes.hip, kind 19): kind 18's kernel with a box
+// index, one workgroup per (box, box tile), grid = nb * tiles box-major.  d_tab: nb x n entries, d_wts: nb x n weights, out: nb boxes of
+// p.oD x oH x oW, p.nTd / nTh / nTw the tiles of one box.  buf_floats: the largest staged patch of the batch (lds_bytes >= 8 * buf_floats).
+hipError_t init_backproject_boxes_kernels();
+hipError_t launch_backproject_boxes(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
+                                    const double* d_wts, int nb, int n, int buf_floats, bool accumulate, const AffineParams& p,
+                                    int lds_bytes, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

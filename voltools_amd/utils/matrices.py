@@ -232,6 +232,31 @@ def backproject_matrices(angles, tilt_axis: int = 1, output_shape=None, image_sh
     return ms
 
 
+def backproject_box_matrices(positions, angles, tilt_axis: int = 1, volume_shape=None, box_shape=None, image_shape=None,
+                             rotation_units: str = 'deg', center: Vec3 = None) -> np.ndarray:
+    """Pull matrices (nb, n, 4, 4), float64, that back-project a tilt series into ``nb`` boxes of shape ``box_shape``
+    (``StaticVolume.backproject_boxes``), box ``b`` being the region of the volume of shape ``volume_shape`` centred at
+    ``positions[b]`` (voxel coordinates of that volume, fractional allowed).
+
+    With ``M_i = backproject_matrices(angles, tilt_axis, volume_shape, image_shape, rotation_units, center)[i]`` and ``c = (box_shape -
+    1) / 2``, entry ``(b, i)`` has ``M_i``'s linear part and the translation ``M_i[:3, 3] + M_i[:3, :3] . (positions[b] - c)``: voxel
+    ``v`` of box ``b`` is voxel ``v + positions[b] - c`` of the full back-projection.
+    """
+    if volume_shape is None or box_shape is None:
+        raise ValueError('volume_shape and box_shape are required')
+    box = _box_shape(box_shape)
+    pos = np.asarray(positions, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3 or pos.shape[0] == 0:
+        raise ValueError('positions must have shape (nb, 3)')
+    m = backproject_matrices(angles, tilt_axis, volume_shape, image_shape, rotation_units, center)
+    c = (np.asarray(box, dtype=np.float64) - 1.0) / 2.0
+    ms = np.empty((pos.shape[0],) + m.shape, dtype=np.float64)
+    ms[:] = m
+    # (nb, n, 3): M_i[:3, :3] . (positions[b] - c)
+    ms[:, :, :3, 3] += np.einsum('irc,bc->bir', m[:, :3, :3], pos - c)
+    return ms
+
+
 def _box_shape(box_shape) -> Tuple[int, int, int]:
     """Three positive ints, or ValueError."""
     try:

@@ -15,7 +15,7 @@ from scipy.ndimage import affine_transform, map_coordinates, spline_filter
 from . import _native
 from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
 from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, place_matrices, tilt_matrices,
-                    backproject_matrices,
+                    backproject_matrices, backproject_box_matrices,
                     get_available_devices, switch_to_device)
 from .utils.matrices import _box_shape
 
@@ -908,6 +908,111 @@ class StaticVolume:
             raise ValueError('output_shape is required')
         ms = backproject_matrices(angles, tilt_axis, output_shape, self.shape[1:], rotation_units, center)
         return self.backproject(ms, output_shape, weights, profile, output, accumulate=accumulate)
+
+    # -- nb boxes of one shape back-projected from the stack in one launch (extension: per-particle reconstruction from a tilt series) ----
+    def backproject_boxes(self, matrices: np.ndarray, box_shape, weights=None, profile: bool = False, output=None, *,
+                          planes=None, accumulate: bool = False, _flags: int = 0,
+                          _max_table_bytes: int = 256 << 20) -> Union[np.ndarray, None]:
+        """``nb`` sub-volumes of shape ``box_shape = (bD, bH, bW)`` from this stack of ``T`` images, ``n`` entries each: ``matrices`` has
+        shape ``(nb, n, 4, 4)`` and entry ``(b, i)`` sends a voxel index inside box ``b`` to a pixel of image ``planes[i]`` (rows 1 and 2
+        count; ``utils.backproject_box_matrices`` builds them from positions and tilt angles).  Box ``b`` holds exactly what
+        ``backproject(matrices[b], box_shape, weights[b], planes=planes, accumulate=...)`` gives, bit for bit on a GPU device, whatever
+        ``nb``, the other boxes and its place in the batch are -- in one kernel launch instead of ``nb``.
+        ``planes``: ``n`` image indices shared by all boxes; None = ``0 .. n-1``, and then ``n`` must equal ``T``.  ``weights``: shape
+        ``(n,)``, used for every box, or ``(nb, n)``; converted to float64; None = ones.  Returns a float32 array ``(nb, bD, bH, bW)``, or
+        fills ``output`` of that shape (numpy, ``vt.empty`` device array, torch-ROCm tensor) and returns None on a GPU device, like
+        ``backproject``; ``accumulate=True`` adds into ``output``, which is then required.  float64 matrices keep their precision;
+        anything else is taken as float32.  The library receives 200 bytes of tables per (box, entry); beyond ``_max_table_bytes`` the
+        call is cut along the box axis into several library calls on consecutive slices of the output, which cannot show in the
+        result."""
+        box = _box_shape(box_shape)
+        ms = np.asarray(matrices)
+        if ms.ndim != 4 or ms.shape[2:] != (4, 4) or ms.shape[0] == 0 or ms.shape[1] == 0:
+            raise ValueError('matrices must have shape (nb, n, 4, 4)')
+        ms = np.ascontiguousarray(ms, dtype=np.float64 if ms.dtype == np.float64 else np.float32)
+        nb, n = ms.shape[:2]
+        if weights is None:
+            w = np.ones((nb, n), dtype=np.float64)
+        else:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape == (n,):
+                w = np.broadcast_to(w, (nb, n))
+            elif w.shape != (nb, n):
+                raise ValueError(f'weights must have shape ({n},) or ({nb}, {n})')
+            w = np.ascontiguousarray(w)
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        if planes is None:
+            if n != self.shape[0]:
+                raise ValueError(f'{n} matrices per box for a stack of {self.shape[0]} images: planes must be given')
+            pl = None
+        else:
+            pl = np.asarray(planes)
+            if pl.shape != (n,) or not np.issubdtype(pl.dtype, np.integer):
+                raise ValueError(f'planes must be {n} integers')
+            if pl.min() < 0 or pl.max() >= self.shape[0]:
+                raise ValueError(f'planes must lie inside [0, {self.shape[0]})')
+            pl = np.ascontiguousarray(pl, dtype=np.int32)
+        shape = (nb,) + box
+        if accumulate and output is None:
+            raise ValueError('accumulate=True adds into output, which must be given')
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.interpolation.startswith('filt_') and not self.stack:
+            raise ValueError('back-projection with a filt_* interpolation needs in-plane coefficients: build the volume with stack=True')
+        if not isinstance(_max_table_bytes, (int, np.integer)) or isinstance(_max_table_bytes, bool) or _max_table_bytes <= 0:
+            raise ValueError('_max_table_bytes must be a positive int')
+        if self.device == 'cpu':
+            res = np.empty(shape, dtype=np.float32)
+            t_start = time.time()
+            for b in range(nb):      # the CPU backproject of that box's matrices, as it stands
+                if accumulate:
+                    res[b] = np.asarray(output[b])
+                    self.backproject(ms[b], box, w[b], output=res[b], planes=pl, accumulate=True)
+                else:
+                    res[b] = self.backproject(ms[b], box, w[b], planes=pl)
+            if profile:
+                print(f'{nb} boxes back-projected from {n} images in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags | (_native.ACCUMULATE if accumulate else 0)
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        pl_ptr = None if pl is None else pl.ctypes.data
+        f64 = ms.dtype == np.float64
+        call = self._lib.vt_volume_backproject_boxes_f64 if f64 else self._lib.vt_volume_backproject_boxes
+        per_call = max(1, int(_max_table_bytes) // (200 * n))      # boxes per library call: 192-byte entry + 8-byte weight per pair
+        box_bytes = 4 * box[0] * box[1] * box[2]
+        for b0 in range(0, nb, per_call):
+            k = min(per_call, nb - b0)
+            rc = call(self._handle, k, n, ms.ctypes.data + b0 * n * 16 * ms.itemsize, pl_ptr, w.ctypes.data + b0 * n * 8, *box,
+                      ptr + b0 * box_bytes, flags)
+            _native.check(rc, 'vt_volume_backproject_boxes')
+        if profile:
+            print(f'{nb} boxes back-projected from {n} images in {self.timer_stop():.3f}ms')
+        return result
+
+    def backproject_boxes_at(self, positions, angles, tilt_axis: int = 1, volume_shape=None, box_shape=None,
+                             rotation_units: str = 'deg', center: Vec3 = None, weights=None, profile: bool = False, output=None, *,
+                             accumulate: bool = False) -> Union[np.ndarray, None]:
+        """``backproject_boxes`` of this stack as the tilt series of a volume of shape ``volume_shape`` (required): box ``b``, of shape
+        ``box_shape`` (required), is the region of ``backproject_tilts(angles, tilt_axis, ..., output_shape=volume_shape)`` centred at
+        ``positions[b]`` (voxel coordinates of that volume, fractional allowed), without the volume ever being formed.  Image ``i`` belongs
+        to ``angles[i]``; the matrices are ``utils.backproject_box_matrices`` for this stack's image shape, in float64."""
+        if volume_shape is None or box_shape is None:
+            raise ValueError('volume_shape and box_shape are required')
+        ms = backproject_box_matrices(positions, angles, tilt_axis, volume_shape, box_shape, self.shape[1:], rotation_units, center)
+        return self.backproject_boxes(ms, box_shape, weights, profile, output, accumulate=accumulate)
 
     def translate(self, translation: Vec3, profile: bool = False, output=None):
         return self.affine(translation_matrix(translation), profile, output)
