@@ -1479,6 +1479,271 @@ int oneshot_pipelined(int dev, const float* h_volume, int D, int H, int W, int i
     return finish(0);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// the host path of a batched call: checks -> tables in v->h_batch_m -> launch parameters -> scratch on the
+// device -> launches -> the record of the launch -> the caller's result.  Each entry point below writes only what is its own.
+// ---------------------------------------------------------------------------------------------------
+
+// ---- checks: the codes and texts of the C ABI; their order within an entry point is part of its behaviour ----
+int check_batch_size(int n) { return n <= 0 ? fail(VT_EINVAL, "batch size %d", n) : 0; }
+
+// `noun`: "box" or "output"
+int check_shape(const char* noun, int d, int h, int w)
+{
+    if (d <= 0 || h <= 0 || w <= 0) return fail(VT_EINVAL, "non-positive %s dims (%d,%d,%d)", noun, d, h, w);
+    if ((int64_t)d * h > 0x7fffffffLL || (int64_t)h * w > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "%s too large", noun);
+    return 0;
+}
+
+// `what`: the operation, as the refusal names it
+int check_whole_volume(const vt_volume* v, const char* what)
+{
+    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
+    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
+        return fail(VT_EINVAL, "%s is available for whole-volume handles only (this one holds a slab window)", what);
+    return 0;
+}
+
+// the handle's device, and no stale sticky error of an unrelated call to fail this call's launch check
+int select_device(const vt_volume* v)
+{
+    const int rc = use_device(v->dev);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    return 0;
+}
+
+// MT: float or double (an entry point that takes both precisions reads the caller's matrices where they are)
+template <typename MT>
+int check_finite_matrices(const MT* m4x4s, size_t n)
+{
+    for (size_t i = 0; i < n * 16; ++i)
+        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    return 0;
+}
+
+int check_finite_weights(const double* weights, size_t n)      // weights == nullptr: ones
+{
+    if (weights)
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %zu is not finite", i);
+    return 0;
+}
+
+// back-projection reads in-plane coefficients, never a padded copy, and one image per entry
+int check_backproject_handle(const vt_volume* v)
+{
+    if (int rc = check_whole_volume(v, "back-projection")) return rc;
+    if (is_filtered(v->interp) && !v->stack)
+        return fail(VT_EUNSUPPORTED, "the handle's coefficients are prefiltered along axis 0 as well: back-projection with a filt_* interpolation "
+                                     "needs in-plane coefficients (create the handle with VT_STACK)");
+    if (v->edge_pad) return fail(VT_EUNSUPPORTED, "back-projection is not available on VT_EDGE_SCIPY handles");
+    return 0;
+}
+
+int check_planes(const vt_volume* v, int n, const int32_t* planes, const char* per)
+{
+    if (planes) {
+        for (int i = 0; i < n; ++i)
+            if (planes[i] < 0 || planes[i] >= v->D) return fail(VT_EINVAL, "plane index %d of entry %d outside [0, %d)", planes[i], i, v->D);
+    } else if (n != v->D) {
+        return fail(VT_EINVAL, "%d matrices%s for a stack of %d images and no plane indices", n, per, v->D);
+    }
+    return 0;
+}
+
+// ---- tables: v->h_batch_m is the staging vector of every batched call, ExtractEntry first, the call's other tables behind them ----
+static_assert(sizeof(ExtractEntry) % sizeof(double) == 0, "the staging vector of doubles holds whole table entries");
+constexpr size_t kEntryDoubles = sizeof(ExtractEntry) / sizeof(double);
+
+ExtractEntry* host_entries(vt_volume* v) { return reinterpret_cast<ExtractEntry*>(v->h_batch_m.data()); }
+const ExtractEntry* device_entries(const vt_volume* v) { return reinterpret_cast<const ExtractEntry*>(v->d_batch_m); }
+
+// The staging vector, `doubles` long, once no copy of an earlier call can still be reading it.  What a call does not write keeps what
+// an earlier call left.
+int begin_tables(vt_volume* v, size_t doubles)
+{
+    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
+    v->h_batch_m.resize(doubles);
+    return 0;
+}
+
+struct TableDims {
+    int L[3];              // the largest staged box over the entries (the two-patch form of back-projection: 2, rows, row stride)
+    int lds_bytes;         // dynamic LDS of the launch
+};
+
+// The table of the three-dimensional family (kinds 11-17): n entries in front of `extra` doubles.  min_lds: what the kernel needs
+// whatever the entries stage.
+int build_box_table(vt_volume* v, const double* m4x4s, int n, size_t extra, int cfg, bool force_direct, int min_lds, TableDims* dims)
+{
+    if (int rc = begin_tables(v, (size_t)n * kEntryDoubles + extra)) return rc;
+    ExtractEntry* const e = host_entries(v);
+    const bool cubic = is_cubic(v->interp);
+    const double pad = (double)v->edge_pad;
+    int64_t lds_bytes = min_lds;
+    int L[3] = {0, 0, 0};
+    for (int i = 0; i < n; ++i) {
+        double m[12];                                   // fold_matrix on a whole-volume handle: the matrix, plus the pad
+        std::memcpy(m, m4x4s + 16 * (size_t)i, sizeof(m));
+        m[3] += pad; m[7] += pad; m[11] += pad;
+        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, &e[i]);
+        if (e[i].tiled) {
+            L[0] = std::max(L[0], e[i].Lz); L[1] = std::max(L[1], e[i].Ly); L[2] = std::max(L[2], e[i].Lx);
+            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e[i].Lz * e[i].Ly * e[i].Lx * 4);
+        }
+    }
+    *dims = TableDims{{L[0], L[1], L[2]}, (int)lds_bytes};
+    return 0;
+}
+
+// The tables of the back-projection family (kinds 18, 19): nb x n entries, then as many weights (nullptr: ones).  Entry k belongs to
+// image planes[k % n] (nullptr: k % n), which is row 0 of its matrix; rows 1 and 2 are the caller's.  An entry stages into LDS when two
+// patches of ITS size fit lds_limit (the kernel keeps the next entry's patch in flight while it samples), whatever the rest of the batch
+// holds; the largest staged patch only sizes the allocation and places the second buffer.  *buf_floats: that patch, in floats.
+// MT: float or double matrices, widened entry by entry (no nb x n x 16 float64 copy of a float32 batch).
+template <typename MT>
+int build_backproject_tables(vt_volume* v, const MT* m4x4s, int nb, int n, const int32_t* planes, const double* weights, int cfg,
+                             bool force_direct, TableDims* dims, int* buf_floats)
+{
+    const size_t total = (size_t)nb * (size_t)n;      // < 2^31 pairs of 200 bytes: no overflow
+    if (int rc = begin_tables(v, total * (kEntryDoubles + 1))) return rc;
+    ExtractEntry* const e = host_entries(v);
+    double* const w = v->h_batch_m.data() + kEntryDoubles * total;
+    const bool cubic = is_cubic(v->interp);
+    int64_t largest = 4;
+    dims->L[0] = 2; dims->L[1] = dims->L[2] = 0;
+    int i = 0;                                        // k % n, without a division per entry
+    for (size_t k = 0; k < total; ++k, i = (i + 1 == n) ? 0 : i + 1) {
+        const MT* a = m4x4s + 16 * k;
+        const double m[12] = {0, 0, 0, (double)(planes ? planes[i] : i), (double)a[4], (double)a[5], (double)a[6], (double)a[7],
+                              (double)a[8], (double)a[9], (double)a[10], (double)a[11]};
+        // tile reach, Q32.32 increments and patch dims by extract_box_dims' rule (no cap: the cap below is on two 2-D patches)
+        extract_fill_entry(m, cfg, cubic, 0x7fffffff, false, &e[k]);
+        const int64_t patch = (int64_t)e[k].Ly * e[k].Lx;
+        if (e[k].tiled && !force_direct && 2 * patch * 4 <= (int64_t)v->lds_limit) {
+            if (patch > largest || dims->L[1] == 0) { dims->L[1] = e[k].Ly; dims->L[2] = e[k].Lx; }
+            largest = std::max(largest, patch);
+        } else {
+            e[k].tiled = 0;
+        }
+        w[k] = weights ? weights[k] : 1.0;
+    }
+    *buf_floats = (int)largest;
+    dims->lds_bytes = (int)(2 * largest * 4);
+    return 0;
+}
+
+// ---- launch parameters ----
+struct BoxTiles {
+    int cfg;               // extract_tile's index
+    int T[3], nT[3];       // the tile, and tiles per axis of the shape
+    int64_t count;         // nT[0] x nT[1] x nT[2]
+};
+
+BoxTiles box_tiles(int cfg, int d, int h, int w)
+{
+    BoxTiles t;
+    t.cfg = cfg;
+    extract_tile(cfg, &t.T[0], &t.T[1], &t.T[2]);
+    const int shape[3] = {d, h, w};
+    for (int k = 0; k < 3; ++k) t.nT[k] = (shape[k] + t.T[k] - 1) / t.T[k];
+    t.count = (int64_t)t.nT[0] * t.nT[1] * t.nT[2];
+    return t;
+}
+
+// AffineParams of a launch that writes shape (d, h, w) from the tables in v->h_batch_m: source dims, output dims, valid interval, and
+// `nT` tiles per axis
+AffineParams box_params(const vt_volume* v, int d, int h, int w, const int nT[3])
+{
+    AffineParams p;
+    std::memset(&p, 0, sizeof(p));
+    TilePlan plan;
+    const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, d, h, w, true);
+    plan_launch(&view, v->h_batch_m.data(), VT_FORCE_DIRECT, &p, &plan);
+    p.nTd = nT[0]; p.nTh = nT[1]; p.nTw = nT[2];
+    return p;
+}
+
+// ---- scratch on the device: grown when too small, never shrunk ----
+// v->h_batch_m, whole, into v->d_batch_m on the handle's stream
+int upload_tables(vt_volume* v)
+{
+    const std::vector<double>& tab = v->h_batch_m;
+    if (v->batch_m_cap < tab.size()) {
+        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
+        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
+        v->batch_m_cap = tab.size();
+    }
+    // (pageable host memory never travels in pieces the runtime would pin in place: PinnedScope, rule 1)
+    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
+                               hipMemcpyHostToDevice, v->stream));
+    return 0;
+}
+
+// v->d_proj_part: the float64 partial sums a launch leaves for its reduction
+int ensure_partials(vt_volume* v, size_t bytes)
+{
+    if (v->proj_part_bytes < bytes) {
+        if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
+        VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), bytes));
+        v->proj_part_bytes = bytes;
+    }
+    return 0;
+}
+
+// ---- the caller's result array: the launches write ptr(), which is `out` itself (VT_OUT_DEVICE) or the handle's staging buffer ----
+struct ResultScope {
+    vt_volume* v;
+    void* out;
+    size_t bytes;
+    bool host_out;
+    PinnedScope pin;       // the caller's array: in (copy_in) and out
+    void* d_out;
+    ResultScope(vt_volume* v_, void* out_, size_t bytes_, bool host_out_)
+        : v(v_), out(out_), bytes(bytes_), host_out(host_out_), pin(host_out_ ? out_ : nullptr, host_out_ ? bytes_ : 0), d_out(out_) {}
+    // copy_in: the caller's contents count (VT_ACCUMULATE, VT_KEEP_OUTSIDE) and go to the device first
+    int open(bool copy_in = false)
+    {
+        if (!host_out) return 0;
+        float* d_stage = nullptr;
+        if (int rc = host_output_buffer(v, (bytes + sizeof(float) - 1) / sizeof(float), &d_stage)) return rc;
+        d_out = d_stage;
+        if (copy_in) VT_HIP(pin.copy(d_out, out, bytes, hipMemcpyHostToDevice, v->stream));
+        return 0;
+    }
+    template <typename T> T* ptr() const { return static_cast<T*>(d_out); }
+    // a host result is complete when this returns; a device result is ordered on the handle's stream
+    int finish()
+    {
+        if (!host_out) return 0;
+        VT_HIP(pin.copy(out, d_out, bytes, hipMemcpyDeviceToHost, v->stream));
+        VT_HIP(hipStreamSynchronize(v->stream));
+        return 0;
+    }
+};
+
+// ---- the record of the launch (vt_volume_info); T, L == nullptr: zeros ----
+void record_launch(vt_volume* v, int kind, const int T[3], const int L[3], int lds_bytes, int64_t grid)
+{
+    v->last_kernel = kind;
+    for (int k = 0; k < 3; ++k) { v->last_tile[k] = T ? T[k] : 0; v->last_lds[k] = L ? L[k] : 0; }
+    v->last_lds_bytes = lds_bytes;
+    v->last_grid = (int)grid;
+}
+
+// the batched direct kernel over `n` matrices of 12 doubles in v->d_batch_m, 65535 at a time, each writing n_out voxels
+int launch_direct_batches(vt_volume* v, int n, float* d_out, size_t n_out, const AffineParams& p)
+{
+    for (int first = 0; first < n; first += 65535) {
+        const int cnt = std::min(65535, n - first);
+        VT_HIP(launch_affine_direct_batch(v->interp, v->d_src, d_out + (size_t)first * n_out, v->d_batch_m + 12 * (size_t)first,
+                                          cnt, p, v->stream));
+    }
+    record_launch(v, 1, nullptr, nullptr, 0, (int64_t)((n_out + 255) / 256));
+    return 0;
+}
+
 // n transforms of one resident volume in one call.  Small volumes (the launch-latency regime: template
 // rotations, sub-tomogram alignment) take ONE launch of the batched direct kernel, 65535 matrices at a time; larger
 // ones are queued back to back on the handle's stream without returning to the caller in between.
@@ -1487,11 +1752,9 @@ int do_affine_batch(vt_volume* v, int n, const double* m4x4s, float* out, int fl
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
     if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    int rc = use_device(v->dev);
-    if (rc) return rc;
+    int rc = check_batch_size(n);
+    if (rc || (rc = use_device(v->dev))) return rc;
     const size_t n_out = (size_t)v->oD * v->oH * v->oW;
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool small = n_out <= (size_t)96 * 96 * 96 && !(flags & VT_FORCE_TILED);
     if (!small) {
         for (int i = 0; i < n; ++i) {
@@ -1500,59 +1763,19 @@ int do_affine_batch(vt_volume* v, int n, const double* m4x4s, float* out, int fl
         }
         return 0;
     }
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
-    // fold the output-plane / slab offsets exactly as do_affine does
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    std::vector<double>& ms = v->h_batch_m;
-    ms.resize((size_t)n * 12);
-    for (int i = 0; i < n; ++i) {
-        const double* a = m4x4s + 16 * (size_t)i;
-        double* m = ms.data() + 12 * (size_t)i;
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
-            m[4 * r + 3] = std::fma(a[4 * r], (double)v->out_plane0, a[4 * r + 3]) + (double)v->edge_pad;
-        }
-        m[3] -= (double)v->plane0;
-    }
+    if ((rc = check_finite_matrices(m4x4s, (size_t)n))) return rc;
+    // 12 doubles per matrix, the output-plane / slab offsets folded exactly as do_affine does
+    if ((rc = begin_tables(v, (size_t)n * 12))) return rc;
+    for (int i = 0; i < n; ++i) fold_matrix(v, m4x4s + 16 * (size_t)i, v->h_batch_m.data() + 12 * (size_t)i);
     AffineParams p;
     std::memset(&p, 0, sizeof(p));
     TilePlan plan;
-    plan_launch(v, ms.data(), (flags & VT_KEEP_OUTSIDE) | VT_FORCE_DIRECT, &p, &plan);   // dims, valid interval, flags
-    if (v->batch_m_cap < ms.size()) {
-        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), ms.size() * sizeof(double)));
-        v->batch_m_cap = ms.size();
-    }
-    // (pageable host memory never travels in pieces the runtime would pin in place: PinnedScope, rule 1)
-    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(ms.data()), ms.size() * sizeof(double),
-                               hipMemcpyHostToDevice, v->stream));
-    float* d_out = out;
-    const size_t total = n_out * (size_t)n;
-    PinnedScope pin(host_out ? out : nullptr, host_out ? total * sizeof(float) : 0);
-    if (host_out) {
-        if (v->scratch_elems < total) {
-            if (v->d_scratch_out) { cached_free(v->dev, v->d_scratch_out, v->scratch_elems * sizeof(float)); v->d_scratch_out = nullptr; v->scratch_elems = 0; }
-            VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_scratch_out), total * sizeof(float)));
-            v->scratch_elems = total;
-        }
-        d_out = v->d_scratch_out;
-        if (flags & VT_KEEP_OUTSIDE) VT_HIP(pin.copy(d_out, out, total * sizeof(float), hipMemcpyHostToDevice, v->stream));
-    }
-    for (int first = 0; first < n; first += 65535) {
-        const int cnt = std::min(65535, n - first);
-        VT_HIP(launch_affine_direct_batch(v->interp, v->d_src, d_out + (size_t)first * n_out, v->d_batch_m + 12 * (size_t)first,
-                                          cnt, p, v->stream));
-    }
-    v->last_kernel = 1;
-    v->last_tile[0] = v->last_tile[1] = v->last_tile[2] = 0;
-    v->last_lds[0] = v->last_lds[1] = v->last_lds[2] = 0;
-    v->last_lds_bytes = 0; v->last_grid = (int)((n_out + 255) / 256);
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+    plan_launch(v, v->h_batch_m.data(), (flags & VT_KEEP_OUTSIDE) | VT_FORCE_DIRECT, &p, &plan);   // dims, valid interval, flags
+    if ((rc = upload_tables(v))) return rc;
+    ResultScope res(v, out, n_out * (size_t)n * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open((flags & VT_KEEP_OUTSIDE) != 0))) return rc;
+    if ((rc = launch_direct_batches(v, n, res.ptr<float>(), n_out, p))) return rc;
+    return res.finish();
 }
 
 // Which box shapes the batched extraction kernel (kind 11) serves by default; the others take the batched direct kernel.
@@ -1572,105 +1795,44 @@ int do_extract(vt_volume* v, int n, const double* m4x4s, int bd, int bh, int bw,
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
-    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "box extraction is available for whole-volume handles only (this one holds a slab window)");
-    int rc = use_device(v->dev);
-    if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_shape("box", bd, bh, bw)) || (rc = check_whole_volume(v, "box extraction")) || (rc = select_device(v)) ||
+        (rc = check_finite_matrices(m4x4s, (size_t)n)))
+        return rc;
 
-    const bool cubic = is_cubic(v->interp);
     const int box[3] = {bd, bh, bw};
     const size_t n_box = (size_t)bd * bh * bw;
-    const size_t total = n_box * (size_t)n;
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool tiled = (flags & VT_FORCE_TILED) || (!(flags & VT_FORCE_DIRECT) && extract_routes_tiled(v->interp, bd, bh, bw));
+    const BoxTiles t = box_tiles(extract_pick_tile(is_cubic(v->interp), box, nullptr), bd, bh, bw);
 
     // the launch's table: ExtractEntry per matrix (kind 11) or 12 doubles per matrix (batched direct kernel)
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    const size_t per = tiled ? sizeof(ExtractEntry) / sizeof(double) : 12;
-    std::vector<double>& tab = v->h_batch_m;
-    tab.resize((size_t)n * per);
-    int wg_per_cu = 0;
-    const int cfg = extract_pick_tile(cubic, box, &wg_per_cu);
-    int T[3];
-    extract_tile(cfg, &T[0], &T[1], &T[2]);
-    int Lmax[3] = {0, 0, 0};
-    int64_t lds_bytes = 16;
-    for (int i = 0; i < n; ++i) {
-        const double* a = m4x4s + 16 * (size_t)i;
-        double m[12];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
-            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
-        }
-        if (tiled) {
-            ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
-            extract_fill_entry(m, cfg, cubic, v->lds_limit, false, e);
-            if (e->tiled) {
-                Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
-                lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
-            }
-        } else {
-            std::memcpy(tab.data() + per * (size_t)i, m, sizeof(m));
-        }
-    }
-    AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    TilePlan plan;
-    {
-        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
-        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
-    }
-    p.nTd = (bd + T[0] - 1) / T[0]; p.nTh = (bh + T[1] - 1) / T[1]; p.nTw = (bw + T[2] - 1) / T[2];
-    const int64_t tiles = (int64_t)p.nTd * p.nTh * p.nTw;
-    if (tiled && tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
-
-    if (v->batch_m_cap < tab.size()) {
-        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-        v->batch_m_cap = tab.size();
-    }
-    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                               hipMemcpyHostToDevice, v->stream));
-    float* d_out = out;
-    PinnedScope pin(host_out ? out : nullptr, host_out ? total * sizeof(float) : 0);
-    if (host_out && (rc = host_output_buffer(v, total, &d_out))) return rc;
-
-    int64_t last_grid = 0;
+    TableDims dims;
     if (tiled) {
-        const int per_launch = (int)std::min<int64_t>(n, 0x7fffffffLL / tiles);
+        if ((rc = build_box_table(v, m4x4s, n, 0, t.cfg, false, 16, &dims))) return rc;
+    } else {
+        if ((rc = begin_tables(v, (size_t)n * 12))) return rc;
+        for (int i = 0; i < n; ++i) fold_matrix(v, m4x4s + 16 * (size_t)i, v->h_batch_m.data() + 12 * (size_t)i);
+    }
+    const AffineParams p = box_params(v, bd, bh, bw, t.nT);
+    if (tiled && t.count > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+
+    if ((rc = upload_tables(v))) return rc;
+    ResultScope res(v, out, n_box * (size_t)n * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open())) return rc;
+    if (tiled) {
+        int64_t last_grid = 0;
+        const int per_launch = (int)std::min<int64_t>(n, 0x7fffffffLL / t.count);
         for (int first = 0; first < n; first += per_launch) {
             const int cnt = std::min(per_launch, n - first);
-            last_grid = tiles * cnt;
-            VT_HIP(launch_extract(cfg, v->interp, v->d_src, d_out + (size_t)first * n_box,
-                                  v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m) + first, p, last_grid, (int)lds_bytes, v->stream));
+            last_grid = t.count * cnt;
+            VT_HIP(launch_extract(t.cfg, v->interp, v->d_src, res.ptr<float>() + (size_t)first * n_box, v->d_zeros, device_entries(v) + first, p,
+                                  last_grid, dims.lds_bytes, v->stream));
         }
-        v->last_kernel = 11;
-        v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-        v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
-        v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)last_grid;
-    } else {
-        for (int first = 0; first < n; first += 65535) {
-            const int cnt = std::min(65535, n - first);
-            VT_HIP(launch_affine_direct_batch(v->interp, v->d_src, d_out + (size_t)first * n_box, v->d_batch_m + 12 * (size_t)first,
-                                              cnt, p, v->stream));
-        }
-        v->last_kernel = 1;
-        v->last_tile[0] = v->last_tile[1] = v->last_tile[2] = 0;
-        v->last_lds[0] = v->last_lds[1] = v->last_lds[2] = 0;
-        v->last_lds_bytes = 0; v->last_grid = (int)((n_box + 255) / 256);
+        record_launch(v, 11, t.T, dims.L, dims.lds_bytes, last_grid);
+    } else if ((rc = launch_direct_batches(v, n, res.ptr<float>(), n_box, p))) {
+        return rc;
     }
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+    return res.finish();
 }
 
 // Axis-0 projection: out[h, w] = sum_d affine(m)[d, h, w]  (see vt_kernels_project.hip)
@@ -1741,10 +1903,7 @@ int do_project(vt_volume* v, const double m4x4[16], float* out, int flags)
         double m2[16] = {1, 0, 0, 0, 0, m[5], m[6], m[7], 0, m[9], m[10], m[11], 0, 0, 0, 1};
         // the helper's planes change with every call: no cached pair copy, and a 2-D image does not need LDS staging
         rc = do_affine(h, m2, out, (flags & VT_OUT_DEVICE) | VT_FORCE_DIRECT);
-        v->last_kernel = 7;
-        v->last_tile[0] = v->last_tile[1] = v->last_tile[2] = 0;
-        v->last_lds[0] = v->last_lds[1] = v->last_lds[2] = 0;
-        v->last_lds_bytes = 0; v->last_grid = 0;
+        record_launch(v, 7, nullptr, nullptr, 0, 0);
         return rc;
     }
 
@@ -1805,30 +1964,19 @@ int do_project_batch(vt_volume* v, int n, const double* m4x4s, int depth, int he
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    if (depth <= 0 || height <= 0 || width <= 0) return fail(VT_EINVAL, "non-positive output dims (%d,%d,%d)", depth, height, width);
-    if ((int64_t)depth * height > 0x7fffffffLL || (int64_t)height * width > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "batched projection is available for whole-volume handles only (this one holds a slab window)");
-    int rc = use_device(v->dev);
-    if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_shape("output", depth, height, width)) || (rc = check_whole_volume(v, "batched projection")) ||
+        (rc = select_device(v)) || (rc = check_finite_matrices(m4x4s, (size_t)n)))
+        return rc;
 
     const size_t n2 = (size_t)height * width;
-    const size_t total = n2 * (size_t)n;
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool fused = (flags & VT_FORCE_TILED) || (!(flags & VT_FORCE_DIRECT) && project_batch_routes_fused(v->interp, depth, height, width));
-
-    float* d_out = out;
-    PinnedScope pin(host_out ? out : nullptr, host_out ? total * sizeof(float) : 0);
+    ResultScope res(v, out, n2 * (size_t)n * sizeof(float), !(flags & VT_OUT_DEVICE));
 
     if (!fused) {
         // the single-matrix path, once per matrix, on the requested output shape (the handle's own shape is put back before the call returns;
         // calls on a handle are serialised).  Each image goes to its place in the device buffer; a host `out` is copied once at the end.
-        if (host_out && (rc = host_output_buffer(v, total, &d_out))) return rc;
+        if ((rc = res.open())) return rc;
         struct ShapeScope {
             vt_volume* v; int d, h, w;
             ShapeScope(vt_volume* v_, int od, int oh, int ow) : v(v_), d(v_->oD), h(v_->oH), w(v_->oW) { v->oD = od; v->oH = oh; v->oW = ow; }
@@ -1836,85 +1984,41 @@ int do_project_batch(vt_volume* v, int n, const double* m4x4s, int depth, int he
         } shape(v, depth, height, width);
         const int lf = (flags & ~(VT_FORCE_DIRECT | VT_FORCE_TILED | VT_KEEP_OUTSIDE)) | VT_OUT_DEVICE;
         for (int i = 0; i < n; ++i)
-            if ((rc = do_project(v, m4x4s + 16 * (size_t)i, d_out + (size_t)i * n2, lf))) return rc;
-    } else {
-        const bool cubic = is_cubic(v->interp);
-        int cfg = 0, nseg = 1, tps = 1, T[3];
-        project_batch_shape_plan(cubic, depth, height, width, &cfg, &nseg, &tps);
-        extract_tile(cfg, &T[0], &T[1], &T[2]);
-
-        VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-        const size_t per = sizeof(ExtractEntry) / sizeof(double);
-        std::vector<double>& tab = v->h_batch_m;
-        tab.resize((size_t)n * per);
-        int Lmax[3] = {0, 0, 0};
-        int64_t lds_bytes = 2048;                         // 256 doubles: the lane groups of the small tiles meet in LDS
-        for (int i = 0; i < n; ++i) {
-            const double* a = m4x4s + 16 * (size_t)i;
-            double m[12];
-            for (int r = 0; r < 3; ++r) {
-                for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
-                m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
-            }
-            ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
-            extract_fill_entry(m, cfg, cubic, v->lds_limit, false, e);
-            if (e->tiled) {
-                Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
-                lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
-            }
-        }
-        AffineParams p;
-        std::memset(&p, 0, sizeof(p));
-        TilePlan plan;
-        {
-            const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, depth, height, width, true);
-            plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, output dims, valid interval
-        }
-        p.nTd = nseg; p.dch = tps;
-        p.nTh = (height + T[1] - 1) / T[1]; p.nTw = (width + T[2] - 1) / T[2];
-        const int64_t units = (int64_t)nseg * p.nTh * p.nTw;
-        if (units > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
-
-        // matrices per launch: the grid limit, and partial sums of no more than max(one output volume in float32, one matrix's partials)
-        int64_t per_launch = std::min<int64_t>(n, 0x7fffffffLL / units);
-        if (nseg > 1) {
-            const size_t image_bytes = (size_t)nseg * n2 * sizeof(double);
-            const size_t cap = std::max((size_t)depth * n2 * sizeof(float), image_bytes);
-            per_launch = std::min<int64_t>(per_launch, (int64_t)(cap / image_bytes));
-            const size_t need = image_bytes * (size_t)per_launch;
-            if (v->proj_part_bytes < need) {
-                if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
-                VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), need));
-                v->proj_part_bytes = need;
-            }
-        }
-        if (v->batch_m_cap < tab.size()) {
-            if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-            VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-            v->batch_m_cap = tab.size();
-        }
-        VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, v->stream));
-        if (host_out && (rc = host_output_buffer(v, total, &d_out))) return rc;
-
-        int64_t last_grid = 0;
-        for (int first = 0; first < n; first += (int)per_launch) {
-            const int cnt = (int)std::min<int64_t>(per_launch, n - first);
-            last_grid = units * cnt;
-            VT_HIP(launch_project_tiled(cfg, v->interp, v->d_src, d_out + (size_t)first * n2, v->d_proj_part, v->d_zeros,
-                                        reinterpret_cast<const ExtractEntry*>(v->d_batch_m) + first, p, last_grid, (int)lds_bytes, v->stream));
-            if (nseg > 1) VT_HIP(launch_project_reduce(v->d_proj_part, d_out + (size_t)first * n2, nseg, (int64_t)n2, cnt, v->stream));
-        }
-        v->last_kernel = 12;
-        v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-        v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
-        v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)last_grid;
+            if ((rc = do_project(v, m4x4s + 16 * (size_t)i, res.ptr<float>() + (size_t)i * n2, lf))) return rc;
+        return res.finish();
     }
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
+    int cfg = 0, nseg = 1, tps = 1;
+    project_batch_shape_plan(is_cubic(v->interp), depth, height, width, &cfg, &nseg, &tps);
+    const BoxTiles t = box_tiles(cfg, depth, height, width);
+
+    TableDims dims;
+    if ((rc = build_box_table(v, m4x4s, n, 0, cfg, false, 2048, &dims))) return rc;      // 256 doubles: the lane groups of the small tiles meet in LDS
+    AffineParams p = box_params(v, depth, height, width, t.nT);
+    p.nTd = nseg; p.dch = tps;                        // depth: segments of tps tiles
+    const int64_t units = (int64_t)nseg * p.nTh * p.nTw;
+    if (units > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
+
+    // matrices per launch: the grid limit, and partial sums of no more than max(one output volume in float32, one matrix's partials)
+    int64_t per_launch = std::min<int64_t>(n, 0x7fffffffLL / units);
+    if (nseg > 1) {
+        const size_t image_bytes = (size_t)nseg * n2 * sizeof(double);
+        const size_t cap = std::max((size_t)depth * n2 * sizeof(float), image_bytes);
+        per_launch = std::min<int64_t>(per_launch, (int64_t)(cap / image_bytes));
+        if ((rc = ensure_partials(v, image_bytes * (size_t)per_launch))) return rc;
     }
-    return 0;
+    if ((rc = upload_tables(v)) || (rc = res.open())) return rc;
+
+    int64_t last_grid = 0;
+    for (int first = 0; first < n; first += (int)per_launch) {
+        const int cnt = (int)std::min<int64_t>(per_launch, n - first);
+        float* const d_img = res.ptr<float>() + (size_t)first * n2;
+        last_grid = units * cnt;
+        VT_HIP(launch_project_tiled(cfg, v->interp, v->d_src, d_img, v->d_proj_part, v->d_zeros, device_entries(v) + first, p, last_grid,
+                                    dims.lds_bytes, v->stream));
+        if (nseg > 1) VT_HIP(launch_project_reduce(v->d_proj_part, d_img, nseg, (int64_t)n2, cnt, v->stream));
+    }
+    record_launch(v, 12, t.T, dims.L, dims.lds_bytes, last_grid);
+    return res.finish();
 }
 
 // One box: the weighted sum of the n boxes do_extract would write (sub-tomogram averaging; symmetrisation with the volume as the box), in
@@ -1924,94 +2028,45 @@ int do_extract_sum(vt_volume* v, int n, const double* m4x4s, const double* weigh
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
-    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "box summation is available for whole-volume handles only (this one holds a slab window)");
-    int rc = use_device(v->dev);
-    if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
-    if (weights)
-        for (int i = 0; i < n; ++i)
-            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %d is not finite", i);
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_shape("box", bd, bh, bw)) || (rc = check_whole_volume(v, "box summation")) || (rc = select_device(v)) ||
+        (rc = check_finite_matrices(m4x4s, (size_t)n)) || (rc = check_finite_weights(weights, (size_t)n)))
+        return rc;
 
-    const bool cubic = is_cubic(v->interp);
     const int box[3] = {bd, bh, bw};
     const size_t n_box = (size_t)bd * bh * bw;
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
-    int cfg = 0, nseg = 1, per_seg = n, T[3];
-    extract_sum_shape_plan(cubic, box, n, &cfg, &nseg, &per_seg);
-    extract_tile(cfg, &T[0], &T[1], &T[2]);
+    int cfg = 0, nseg = 1, per_seg = n;
+    extract_sum_shape_plan(is_cubic(v->interp), box, n, &cfg, &nseg, &per_seg);
+    const BoxTiles t = box_tiles(cfg, bd, bh, bw);
 
     // the launch's tables: one ExtractEntry per matrix, then the n weights
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    const size_t per = sizeof(ExtractEntry) / sizeof(double);
-    std::vector<double>& tab = v->h_batch_m;
-    tab.resize((size_t)n * (per + 1));
-    int Lmax[3] = {0, 0, 0};
-    int64_t lds_bytes = 16;
-    for (int i = 0; i < n; ++i) {
-        const double* a = m4x4s + 16 * (size_t)i;
-        double m[12];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
-            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
-        }
-        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
-        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, e);
-        if (e->tiled) {
-            Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
-            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
-        }
-        tab[per * (size_t)n + (size_t)i] = weights ? weights[i] : 1.0;
-    }
-    AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    TilePlan plan;
-    {
-        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
-        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
-    }
-    p.nTd = (bd + T[0] - 1) / T[0]; p.nTh = (bh + T[1] - 1) / T[1]; p.nTw = (bw + T[2] - 1) / T[2];
-    const int64_t grid = (int64_t)p.nTd * p.nTh * p.nTw * nseg;
+    TableDims dims;
+    if ((rc = build_box_table(v, m4x4s, n, (size_t)n, cfg, force_direct, 16, &dims))) return rc;
+    double* const w = v->h_batch_m.data() + kEntryDoubles * (size_t)n;
+    for (int i = 0; i < n; ++i) w[i] = weights ? weights[i] : 1.0;
+    const AffineParams p = box_params(v, bd, bh, bw, t.nT);
+    const int64_t grid = t.count * nseg;
     if (grid > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
 
-    if (nseg > 1) {
-        const size_t need = (size_t)nseg * n_box * sizeof(double);       // tiles x nseg < 2048: under 64 MiB
-        if (v->proj_part_bytes < need) {
-            if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
-            VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), need));
-            v->proj_part_bytes = need;
-        }
-    }
-    if (v->batch_m_cap < tab.size()) {
-        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-        v->batch_m_cap = tab.size();
-    }
-    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                               hipMemcpyHostToDevice, v->stream));
-    float* d_out = out;
-    PinnedScope pin(host_out ? out : nullptr, host_out ? n_box * sizeof(float) : 0);
-    if (host_out && (rc = host_output_buffer(v, n_box, &d_out))) return rc;
+    if (nseg > 1 && (rc = ensure_partials(v, (size_t)nseg * n_box * sizeof(double)))) return rc;      // tiles x nseg < 2048: under 64 MiB
+    if ((rc = upload_tables(v))) return rc;
+    ResultScope res(v, out, n_box * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open())) return rc;
 
-    VT_HIP(launch_extract_sum(cfg, v->interp, v->d_src, d_out, v->d_proj_part, v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m),
-                              v->d_batch_m + per * (size_t)n, n, per_seg, nseg, p, (int)lds_bytes, v->stream));
-    if (nseg > 1) VT_HIP(launch_project_reduce(v->d_proj_part, d_out, nseg, (int64_t)n_box, 1, v->stream));
-    v->last_kernel = 13;
-    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-    v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
-    v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)grid;
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, n_box * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+    VT_HIP(launch_extract_sum(cfg, v->interp, v->d_src, res.ptr<float>(), v->d_proj_part, v->d_zeros, device_entries(v),
+                              v->d_batch_m + kEntryDoubles * (size_t)n, n, per_seg, nseg, p, dims.lds_bytes, v->stream));
+    if (nseg > 1) VT_HIP(launch_project_reduce(v->d_proj_part, res.ptr<float>(), nseg, (int64_t)n_box, 1, v->stream));
+    record_launch(v, 13, t.T, dims.L, dims.lds_bytes, grid);
+    return res.finish();
+}
+
+// The part of the two scoring entry points' checks that is the same: kernels 14 and 15 index a template and the mask with 32 bits.
+int check_dot_box(const vt_volume* v, int bd, int bh, int bw)
+{
+    if (int rc = check_shape("box", bd, bh, bw)) return rc;
+    if ((int64_t)(bd + 16) * bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    return check_whole_volume(v, "box scoring");
 }
 
 // n x 3 float64: (sum mask * B_i, sum mask * B_i^2, sum tmpl * B_i) over the voxels of each box B_i do_extract would write (scoring n candidate
@@ -2021,109 +2076,45 @@ int do_extract_dot(vt_volume* v, int n, const double* m4x4s, const float* tmpl, 
 {
     if (!v || !m4x4s || !tmpl || !out) return fail(VT_EINVAL, "NULL argument");
     if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
-    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
-    if ((int64_t)(bd + 16) * bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");      // kernel 14 indexes tmpl / mask with 32 bits
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "box scoring is available for whole-volume handles only (this one holds a slab window)");
-    int rc = use_device(v->dev);
-    if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_dot_box(v, bd, bh, bw)) || (rc = select_device(v)) || (rc = check_finite_matrices(m4x4s, (size_t)n))) return rc;
     const size_t n_box = (size_t)bd * bh * bw;
     for (size_t i = 0; i < n_box; ++i) {
         if (!std::isfinite(tmpl[i])) return fail(VT_EINVAL, "template voxel %zu is not finite", i);
         if (mask && !std::isfinite(mask[i])) return fail(VT_EINVAL, "mask voxel %zu is not finite", i);
     }
 
-    const bool cubic = is_cubic(v->interp);
     const int box[3] = {bd, bh, bw};
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
-    const int cfg = extract_pick_tile(cubic, box, nullptr);
-    int T[3];
-    extract_tile(cfg, &T[0], &T[1], &T[2]);
+    const BoxTiles t = box_tiles(extract_pick_tile(is_cubic(v->interp), box, nullptr), bd, bh, bw);
 
     // the call's tables in one staging vector: one ExtractEntry per matrix, then the template and the mask (float32, padded to 16 bytes each)
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    const size_t per = sizeof(ExtractEntry) / sizeof(double);
     const size_t box_dbl = (n_box + 3) / 4 * 2;       // doubles that hold one box of float32
-    std::vector<double>& tab = v->h_batch_m;
-    tab.resize((size_t)n * per + box_dbl * (mask ? 2 : 1));
-    int Lmax[3] = {0, 0, 0};
-    int64_t lds_bytes = extract_dot_min_lds();
-    for (int i = 0; i < n; ++i) {
-        const double* a = m4x4s + 16 * (size_t)i;
-        double m[12];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
-            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
-        }
-        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
-        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, e);
-        if (e->tiled) {
-            Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
-            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
-        }
-    }
-    std::memcpy(tab.data() + per * (size_t)n, tmpl, n_box * sizeof(float));
-    if (mask) std::memcpy(tab.data() + per * (size_t)n + box_dbl, mask, n_box * sizeof(float));
-    AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    TilePlan plan;
-    {
-        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
-        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
-    }
-    p.nTd = (bd + T[0] - 1) / T[0]; p.nTh = (bh + T[1] - 1) / T[1]; p.nTw = (bw + T[2] - 1) / T[2];
-    const int64_t tiles = (int64_t)p.nTd * p.nTh * p.nTw;
-    if (tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    const size_t tmpl_at = kEntryDoubles * (size_t)n, mask_at = tmpl_at + box_dbl;
+    TableDims dims;
+    if ((rc = build_box_table(v, m4x4s, n, box_dbl * (mask ? 2 : 1), t.cfg, force_direct, extract_dot_min_lds(), &dims))) return rc;
+    std::memcpy(v->h_batch_m.data() + tmpl_at, tmpl, n_box * sizeof(float));
+    if (mask) std::memcpy(v->h_batch_m.data() + mask_at, mask, n_box * sizeof(float));
+    const AffineParams p = box_params(v, bd, bh, bw, t.nT);
+    if (t.count > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
 
     // matrices per launch: their partials stay within the cap (one matrix's partials at least), the grid within 2^31
-    const int64_t part_one = tiles * 3 * (int64_t)sizeof(double);
-    const int per_launch = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n, v->tune.dot_part_cap / part_one, 0x7fffffffLL / tiles}));
-    const size_t need = (size_t)per_launch * (size_t)part_one;
-    if (v->proj_part_bytes < need) {
-        if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
-        VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), need));
-        v->proj_part_bytes = need;
-    }
-    if (v->batch_m_cap < tab.size()) {
-        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-        v->batch_m_cap = tab.size();
-    }
-    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                               hipMemcpyHostToDevice, v->stream));
-    const float* d_tmpl = reinterpret_cast<const float*>(v->d_batch_m + per * (size_t)n);
-    const float* d_mask = mask ? reinterpret_cast<const float*>(v->d_batch_m + per * (size_t)n + box_dbl) : nullptr;
-    double* d_out = out;
-    const size_t out_bytes = (size_t)n * 3 * sizeof(double);
-    PinnedScope pin(host_out ? out : nullptr, host_out ? out_bytes : 0);
-    if (host_out) {
-        float* d_stage = nullptr;
-        if ((rc = host_output_buffer(v, (size_t)n * 6, &d_stage))) return rc;
-        d_out = reinterpret_cast<double*>(d_stage);
-    }
+    const int64_t part_one = t.count * 3 * (int64_t)sizeof(double);
+    const int per_launch = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n, v->tune.dot_part_cap / part_one, 0x7fffffffLL / t.count}));
+    if ((rc = ensure_partials(v, (size_t)per_launch * (size_t)part_one)) || (rc = upload_tables(v))) return rc;
+    const float* d_tmpl = reinterpret_cast<const float*>(v->d_batch_m + tmpl_at);
+    const float* d_mask = mask ? reinterpret_cast<const float*>(v->d_batch_m + mask_at) : nullptr;
+    ResultScope res(v, out, (size_t)n * 3 * sizeof(double), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open())) return rc;
 
     int last_cnt = 0;
     for (int first = 0; first < n; first += per_launch) {
         last_cnt = std::min(per_launch, n - first);
-        VT_HIP(launch_extract_dot(cfg, v->interp, v->d_src, d_out + (size_t)first * 3, v->d_proj_part, v->d_zeros,
-                                  reinterpret_cast<const ExtractEntry*>(v->d_batch_m) + first, d_tmpl, d_mask, last_cnt, p, (int)lds_bytes, v->stream));
+        VT_HIP(launch_extract_dot(t.cfg, v->interp, v->d_src, res.ptr<double>() + (size_t)first * 3, v->d_proj_part, v->d_zeros,
+                                  device_entries(v) + first, d_tmpl, d_mask, last_cnt, p, dims.lds_bytes, v->stream));
     }
-    v->last_kernel = 14;
-    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-    v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
-    v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)(tiles * last_cnt);
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, out_bytes, hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+    record_launch(v, 14, t.T, dims.L, dims.lds_bytes, t.count * last_cnt);
+    return res.finish();
 }
 
 // n x (2 + k) float64: do_extract_dot's two mask sums followed by one template sum per template of the stack (scoring n candidate poses
@@ -2135,30 +2126,19 @@ int do_extract_dot_multi(vt_volume* v, int n, const double* m4x4s, int k, const 
 {
     if (!v || !m4x4s || !tmpls || !out) return fail(VT_EINVAL, "NULL argument");
     if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    if (k <= 0) return fail(VT_EINVAL, "template count %d", k);
-    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
-    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
-    if ((int64_t)(bd + 16) * bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");      // kernel 15 indexes a template / the mask with 32 bits
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "box scoring is available for whole-volume handles only (this one holds a slab window)");
-
-    const bool cubic = is_cubic(v->interp);
-    const int box[3] = {bd, bh, bw};
-    const int cfg = extract_pick_tile(cubic, box, nullptr);
-    int T[3];
-    extract_tile(cfg, &T[0], &T[1], &T[2]);
-    const int64_t tiles = (int64_t)((bd + T[0] - 1) / T[0]) * ((bh + T[1] - 1) / T[1]) * ((bw + T[2] - 1) / T[2]);
-    const int64_t ncol = 2 + (int64_t)k;
-    if (tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
-    if (tiles * ncol > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box tiles x (2 + k) = %lld exceeds 2^31 - 1", (long long)(tiles * ncol));
-
-    int rc = use_device(v->dev);
+    int rc = check_batch_size(n);
     if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    if (k <= 0) return fail(VT_EINVAL, "template count %d", k);
+    if ((rc = check_dot_box(v, bd, bh, bw))) return rc;
+
+    const int box[3] = {bd, bh, bw};
+    const BoxTiles t = box_tiles(extract_pick_tile(is_cubic(v->interp), box, nullptr), bd, bh, bw);
+    const int64_t ncol = 2 + (int64_t)k;
+    if (t.count > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    if (t.count * ncol > 0x7fffffffLL)
+        return fail(VT_EUNSUPPORTED, "box tiles x (2 + k) = %lld exceeds 2^31 - 1", (long long)(t.count * ncol));
+
+    if ((rc = select_device(v)) || (rc = check_finite_matrices(m4x4s, (size_t)n))) return rc;
     const size_t n_box = (size_t)bd * bh * bw;
     for (size_t j = 0; j < (size_t)k; ++j) {
         const float* tj = tmpls + j * n_box;
@@ -2169,87 +2149,36 @@ int do_extract_dot_multi(vt_volume* v, int n, const double* m4x4s, int k, const 
         for (size_t i = 0; i < n_box; ++i)
             if (!std::isfinite(mask[i])) return fail(VT_EINVAL, "mask voxel %zu is not finite", i);
 
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
 
     // the call's tables in one staging vector: one ExtractEntry per matrix, then the k templates back to back and the mask (float32,
     // the stack and the mask padded to 16 bytes each)
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    const size_t per = sizeof(ExtractEntry) / sizeof(double);
     const size_t stack_dbl = ((size_t)k * n_box + 3) / 4 * 2;      // doubles that hold the stack of float32 templates
     const size_t box_dbl = (n_box + 3) / 4 * 2;                    // ... and one box
-    std::vector<double>& tab = v->h_batch_m;
-    tab.resize((size_t)n * per + stack_dbl + (mask ? box_dbl : 0));
-    int Lmax[3] = {0, 0, 0};
-    int64_t lds_bytes = extract_dot_min_lds();
-    for (int i = 0; i < n; ++i) {
-        const double* a = m4x4s + 16 * (size_t)i;
-        double m[12];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
-            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
-        }
-        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
-        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, e);
-        if (e->tiled) {
-            Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
-            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
-        }
-    }
-    std::memcpy(tab.data() + per * (size_t)n, tmpls, (size_t)k * n_box * sizeof(float));
-    if (mask) std::memcpy(tab.data() + per * (size_t)n + stack_dbl, mask, n_box * sizeof(float));
-    AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    TilePlan plan;
-    {
-        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
-        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
-    }
-    p.nTd = (bd + T[0] - 1) / T[0]; p.nTh = (bh + T[1] - 1) / T[1]; p.nTw = (bw + T[2] - 1) / T[2];
+    const size_t tmpls_at = kEntryDoubles * (size_t)n, mask_at = tmpls_at + stack_dbl;
+    TableDims dims;
+    if ((rc = build_box_table(v, m4x4s, n, stack_dbl + (mask ? box_dbl : 0), t.cfg, force_direct, extract_dot_min_lds(), &dims))) return rc;
+    std::memcpy(v->h_batch_m.data() + tmpls_at, tmpls, (size_t)k * n_box * sizeof(float));
+    if (mask) std::memcpy(v->h_batch_m.data() + mask_at, mask, n_box * sizeof(float));
+    const AffineParams p = box_params(v, bd, bh, bw, t.nT);
 
     // matrices per launch: their partials stay within the cap (one matrix's partials at least), the grid within 2^31
-    const int64_t part_one = tiles * ncol * (int64_t)sizeof(double);
-    const int per_launch = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n, v->tune.dot_part_cap / part_one, 0x7fffffffLL / tiles}));
-    const size_t need = (size_t)per_launch * (size_t)part_one;
-    if (v->proj_part_bytes < need) {
-        if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
-        VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), need));
-        v->proj_part_bytes = need;
-    }
-    if (v->batch_m_cap < tab.size()) {
-        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-        v->batch_m_cap = tab.size();
-    }
-    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                               hipMemcpyHostToDevice, v->stream));
-    const float* d_tmpls = reinterpret_cast<const float*>(v->d_batch_m + per * (size_t)n);
-    const float* d_mask = mask ? reinterpret_cast<const float*>(v->d_batch_m + per * (size_t)n + stack_dbl) : nullptr;
-    double* d_out = out;
-    const size_t out_bytes = (size_t)n * (size_t)ncol * sizeof(double);
-    PinnedScope pin(host_out ? out : nullptr, host_out ? out_bytes : 0);
-    if (host_out) {
-        float* d_stage = nullptr;
-        if ((rc = host_output_buffer(v, (size_t)n * (size_t)ncol * 2, &d_stage))) return rc;
-        d_out = reinterpret_cast<double*>(d_stage);
-    }
+    const int64_t part_one = t.count * ncol * (int64_t)sizeof(double);
+    const int per_launch = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n, v->tune.dot_part_cap / part_one, 0x7fffffffLL / t.count}));
+    if ((rc = ensure_partials(v, (size_t)per_launch * (size_t)part_one)) || (rc = upload_tables(v))) return rc;
+    const float* d_tmpls = reinterpret_cast<const float*>(v->d_batch_m + tmpls_at);
+    const float* d_mask = mask ? reinterpret_cast<const float*>(v->d_batch_m + mask_at) : nullptr;
+    ResultScope res(v, out, (size_t)n * (size_t)ncol * sizeof(double), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open())) return rc;
 
     int last_cnt = 0;
     for (int first = 0; first < n; first += per_launch) {
         last_cnt = std::min(per_launch, n - first);
-        VT_HIP(launch_extract_dot_multi(cfg, v->interp, v->d_src, d_out + (size_t)first * (size_t)ncol, v->d_proj_part, v->d_zeros,
-                                        reinterpret_cast<const ExtractEntry*>(v->d_batch_m) + first, d_tmpls, d_mask, k, last_cnt, p,
-                                        (int)lds_bytes, v->stream));
+        VT_HIP(launch_extract_dot_multi(t.cfg, v->interp, v->d_src, res.ptr<double>() + (size_t)first * (size_t)ncol, v->d_proj_part, v->d_zeros,
+                                        device_entries(v) + first, d_tmpls, d_mask, k, last_cnt, p, dims.lds_bytes, v->stream));
     }
-    v->last_kernel = 15;
-    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-    v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
-    v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)(tiles * last_cnt);
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, out_bytes, hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+    record_launch(v, 15, t.T, dims.L, dims.lds_bytes, t.count * last_cnt);
+    return res.finish();
 }
 
 // g boxes: column j of the n x g weights applied to the n boxes do_extract would write, box j holding the bits do_extract_sum gives for
@@ -2260,37 +2189,28 @@ int do_extract_sum_multi(vt_volume* v, int n, const double* m4x4s, int g, const 
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
+    int rc = check_batch_size(n);
+    if (rc) return rc;
     if (g <= 0) return fail(VT_EINVAL, "column count %d", g);
     if (!weights) return fail(VT_EINVAL, "NULL weights");
-    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
-    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "box summation is available for whole-volume handles only (this one holds a slab window)");
-    int rc = use_device(v->dev);
-    if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
+    if ((rc = check_shape("box", bd, bh, bw)) || (rc = check_whole_volume(v, "box summation")) || (rc = select_device(v)) ||
+        (rc = check_finite_matrices(m4x4s, (size_t)n)))
+        return rc;
     for (size_t i = 0; i < (size_t)n * (size_t)g; ++i)
         if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight (%zu, %zu) is not finite", i / (size_t)g, i % (size_t)g);
 
-    const bool cubic = is_cubic(v->interp);
     const int box[3] = {bd, bh, bw};
     const size_t n_box = (size_t)bd * bh * bw;
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
-    int cfg = 0, nseg = 1, per_seg = n, T[3];
-    extract_sum_shape_plan(cubic, box, n, &cfg, &nseg, &per_seg);      // do_extract_sum's, whatever g is: every column sees its segments
-    extract_tile(cfg, &T[0], &T[1], &T[2]);
+    int cfg = 0, nseg = 1, per_seg = n;
+    extract_sum_shape_plan(is_cubic(v->interp), box, n, &cfg, &nseg, &per_seg);      // do_extract_sum's, whatever g is: every column sees its segments
+    const BoxTiles t = box_tiles(cfg, bd, bh, bw);
     const int GC = extract_sum_multi_chunk(cfg);
-    const int64_t tiles = (int64_t)((bd + T[0] - 1) / T[0]) * ((bh + T[1] - 1) / T[1]) * ((bw + T[2] - 1) / T[2]);
-    if (tiles * nseg > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    if (t.count * nseg > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
 
     // columns per launch: whole chunks, at least one; their partials stay within the cap, the grid within 2^31
     const int64_t chunks_all = ((int64_t)g + GC - 1) / GC;
-    int64_t chunks_per = std::min<int64_t>(chunks_all, 0x7fffffffLL / (tiles * nseg));
+    int64_t chunks_per = std::min<int64_t>(chunks_all, 0x7fffffffLL / (t.count * nseg));
     if (nseg > 1) {
         const int64_t part_chunk = (int64_t)GC * nseg * (int64_t)n_box * (int64_t)sizeof(double);
         chunks_per = std::min<int64_t>(chunks_per, v->tune.dot_part_cap / part_chunk);
@@ -2298,76 +2218,33 @@ int do_extract_sum_multi(vt_volume* v, int n, const double* m4x4s, int g, const 
     chunks_per = std::max<int64_t>(1, chunks_per);
     const int cols_per = (int)std::min<int64_t>(g, chunks_per * GC);
 
-    // the call's tables in one staging vector: one ExtractEntry per matrix, then the n x g weights
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    const size_t per = sizeof(ExtractEntry) / sizeof(double);
-    std::vector<double>& tab = v->h_batch_m;
-    tab.assign((size_t)n * (per + (size_t)g) + 8, 0.0);      // eight doubles of slack behind the last row (a chunk is at most eight columns wide)
-    int Lmax[3] = {0, 0, 0};
-    int64_t lds_bytes = 16;
-    for (int i = 0; i < n; ++i) {
-        const double* a = m4x4s + 16 * (size_t)i;
-        double m[12];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
-            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
-        }
-        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
-        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, e);
-        if (e->tiled) {
-            Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
-            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
-        }
-    }
-    std::memcpy(tab.data() + per * (size_t)n, weights, (size_t)n * (size_t)g * sizeof(double));
-    AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    TilePlan plan;
-    {
-        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
-        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
-    }
-    p.nTd = (bd + T[0] - 1) / T[0]; p.nTh = (bh + T[1] - 1) / T[1]; p.nTw = (bw + T[2] - 1) / T[2];
-    if (tiles * nseg * (((int64_t)cols_per + GC - 1) / GC) > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
+    // the call's tables in one staging vector: one ExtractEntry per matrix, then the n x g weights, then eight doubles of zeros behind the
+    // last row (a chunk is at most eight columns wide)
+    const size_t n_wts = (size_t)n * (size_t)g;
+    TableDims dims;
+    if ((rc = build_box_table(v, m4x4s, n, n_wts + 8, cfg, force_direct, 16, &dims))) return rc;
+    double* const w = v->h_batch_m.data() + kEntryDoubles * (size_t)n;
+    std::memcpy(w, weights, n_wts * sizeof(double));
+    std::fill(w + n_wts, w + n_wts + 8, 0.0);
+    const AffineParams p = box_params(v, bd, bh, bw, t.nT);
+    if (t.count * nseg * (((int64_t)cols_per + GC - 1) / GC) > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
 
-    if (nseg > 1) {
-        const size_t need = (size_t)cols_per * (size_t)nseg * n_box * sizeof(double);
-        if (v->proj_part_bytes < need) {
-            if (v->d_proj_part) { cached_free(v->dev, v->d_proj_part, v->proj_part_bytes); v->d_proj_part = nullptr; v->proj_part_bytes = 0; }
-            VT_HIP(cached_malloc(v->dev, reinterpret_cast<void**>(&v->d_proj_part), need));
-            v->proj_part_bytes = need;
-        }
-    }
-    if (v->batch_m_cap < tab.size()) {
-        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-        v->batch_m_cap = tab.size();
-    }
-    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                               hipMemcpyHostToDevice, v->stream));
-    const size_t total = (size_t)g * n_box;
-    float* d_out = out;
-    PinnedScope pin(host_out ? out : nullptr, host_out ? total * sizeof(float) : 0);
-    if (host_out && (rc = host_output_buffer(v, total, &d_out))) return rc;
+    if (nseg > 1 && (rc = ensure_partials(v, (size_t)cols_per * (size_t)nseg * n_box * sizeof(double)))) return rc;
+    if ((rc = upload_tables(v))) return rc;
+    ResultScope res(v, out, (size_t)g * n_box * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open())) return rc;
 
     int64_t last_grid = 0;
     for (int first = 0; first < g; first += cols_per) {
         const int cnt = std::min(cols_per, g - first);
-        VT_HIP(launch_extract_sum_multi(cfg, v->interp, v->d_src, d_out + (size_t)first * n_box, v->d_proj_part, v->d_zeros,
-                                        reinterpret_cast<const ExtractEntry*>(v->d_batch_m), v->d_batch_m + per * (size_t)n + first, n,
-                                        per_seg, nseg, g, cnt, p, (int)lds_bytes, v->stream));
-        if (nseg > 1) VT_HIP(launch_project_reduce(v->d_proj_part, d_out + (size_t)first * n_box, nseg, (int64_t)n_box, cnt, v->stream));
-        last_grid = tiles * nseg * ((cnt + GC - 1) / GC);
+        float* const d_boxes = res.ptr<float>() + (size_t)first * n_box;
+        VT_HIP(launch_extract_sum_multi(cfg, v->interp, v->d_src, d_boxes, v->d_proj_part, v->d_zeros, device_entries(v),
+                                        v->d_batch_m + kEntryDoubles * (size_t)n + first, n, per_seg, nseg, g, cnt, p, dims.lds_bytes, v->stream));
+        if (nseg > 1) VT_HIP(launch_project_reduce(v->d_proj_part, d_boxes, nseg, (int64_t)n_box, cnt, v->stream));
+        last_grid = t.count * nseg * ((cnt + GC - 1) / GC);
     }
-    v->last_kernel = 16;
-    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-    v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
-    v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)last_grid;
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, total * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+    record_launch(v, 16, t.T, dims.L, dims.lds_bytes, last_grid);
+    return res.finish();
 }
 
 // Output tiles whose base can pass place_tiled's tile test (any_valid) for entry e, as an axis-aligned range of tile indices per axis
@@ -2423,75 +2300,38 @@ int do_place(vt_volume* v, int n, const double* m4x4s, const double* weights, in
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    if (od <= 0 || oh <= 0 || ow <= 0) return fail(VT_EINVAL, "non-positive output dims (%d,%d,%d)", od, oh, ow);
-    if ((int64_t)od * oh > 0x7fffffffLL || (int64_t)oh * ow > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "placing copies is available for whole-volume handles only (this one holds a slab window)");
-    int rc = use_device(v->dev);
-    if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
-    if (weights)
-        for (int i = 0; i < n; ++i)
-            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %d is not finite", i);
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_shape("output", od, oh, ow)) || (rc = check_whole_volume(v, "placing copies")) || (rc = select_device(v)) ||
+        (rc = check_finite_matrices(m4x4s, (size_t)n)) || (rc = check_finite_weights(weights, (size_t)n)))
+        return rc;
 
-    const bool cubic = is_cubic(v->interp);
     const int shape[3] = {od, oh, ow};
     const size_t n_out = (size_t)od * oh * ow;
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
     const bool accumulate = (flags & VT_ACCUMULATE) != 0;
     const bool dense = (flags & VT_PLACE_DENSE) != 0;
-    const int cfg = extract_pick_tile(cubic, shape, nullptr);      // a function of (output shape, interpolation): do_extract_sum's tile
-    int T[3];
-    extract_tile(cfg, &T[0], &T[1], &T[2]);
-    const int nT[3] = {(od + T[0] - 1) / T[0], (oh + T[1] - 1) / T[1], (ow + T[2] - 1) / T[2]};
-    const int64_t tiles = (int64_t)nT[0] * nT[1] * nT[2];
-    if (tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large (%lld tiles)", (long long)tiles);
+    // a function of (output shape, interpolation): do_extract_sum's tile
+    const BoxTiles t = box_tiles(extract_pick_tile(is_cubic(v->interp), shape, nullptr), od, oh, ow);
+    const int* const nT = t.nT;
+    if (t.count > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large (%lld tiles)", (long long)t.count);
 
     // the launch's tables: one ExtractEntry per matrix, then the n weights, then (below) the lists
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    const size_t per = sizeof(ExtractEntry) / sizeof(double);
+    const size_t ints_at = (size_t)n * (kEntryDoubles + 1);
+    TableDims dims;
+    if ((rc = build_box_table(v, m4x4s, n, (size_t)n, t.cfg, force_direct, 16, &dims))) return rc;
     std::vector<double>& tab = v->h_batch_m;
-    tab.resize((size_t)n * (per + 1));
-    int Lmax[3] = {0, 0, 0};
-    int64_t lds_bytes = 16;
-    for (int i = 0; i < n; ++i) {
-        const double* a = m4x4s + 16 * (size_t)i;
-        double m[12];
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 4; ++c) m[4 * r + c] = a[4 * r + c];
-            m[4 * r + 3] += (double)v->edge_pad;      // VT_EDGE_SCIPY: resident coordinate = volume coordinate + pad
-        }
-        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
-        extract_fill_entry(m, cfg, cubic, v->lds_limit, force_direct, e);
-        if (e->tiled) {
-            Lmax[0] = std::max(Lmax[0], e->Lz); Lmax[1] = std::max(Lmax[1], e->Ly); Lmax[2] = std::max(Lmax[2], e->Lx);
-            lds_bytes = std::max<int64_t>(lds_bytes, (int64_t)e->Lz * e->Ly * e->Lx * 4);
-        }
-        tab[per * (size_t)n + (size_t)i] = weights ? weights[i] : 1.0;
-    }
-    AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    TilePlan plan;
-    {
-        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, od, oh, ow, true);
-        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, output dims, valid interval
-    }
-    p.nTd = nT[0]; p.nTh = nT[1]; p.nTw = nT[2];
+    for (int i = 0; i < n; ++i) tab[kEntryDoubles * (size_t)n + (size_t)i] = weights ? weights[i] : 1.0;
+    const AffineParams p = box_params(v, od, oh, ow, nT);
 
     // ---- binning: count, then fill, both in ascending entry order, so every list is ascending by construction; O(sum of candidate tiles) ----
     std::vector<int> range((size_t)n * 6);
-    std::vector<int> cursor((size_t)tiles, 0);        // per tile: entries listed, then the write position of its list
+    std::vector<int> cursor((size_t)t.count, 0);      // per tile: entries listed, then the write position of its list
     int64_t total = 0;
     for (int i = 0; i < n; ++i) {
         int* lo = &range[6 * (size_t)i];
         int* hi = lo + 3;
         if (dense) for (int k = 0; k < 3; ++k) { lo[k] = 0; hi[k] = nT[k] - 1; }
-        else place_tile_range(*reinterpret_cast<const ExtractEntry*>(tab.data() + per * (size_t)i), p, T, nT, lo, hi);
+        else place_tile_range(host_entries(v)[i], p, t.T, nT, lo, hi);
         if (lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) { lo[0] = 0; hi[0] = -1; continue; }
         total += (int64_t)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1);
         if (total > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "tile lists too long (more than 2^31 - 1 (tile, matrix) pairs)");
@@ -2502,20 +2342,19 @@ int do_place(vt_volume* v, int n, const double* m4x4s, const double* weights, in
             }
     }
     int64_t n_tiles = 0;
-    for (int64_t t = 0; t < tiles; ++t) n_tiles += cursor[(size_t)t] > 0;
+    for (int64_t k = 0; k < t.count; ++k) n_tiles += cursor[(size_t)k] > 0;
     const size_t ints = n_tiles > 0 ? (size_t)(2 * n_tiles + 1 + total) : 0;      // tile ids, offsets, list entries
-    const size_t ints_at = (size_t)n * (per + 1);
     tab.resize(ints_at + (ints + 1) / 2);
     int* const ids = reinterpret_cast<int*>(tab.data() + ints_at);
     int* const offs = ids + n_tiles;
     int* const idx = offs + n_tiles + 1;
     if (n_tiles > 0) {
         int64_t k = 0, at = 0;
-        for (int64_t t = 0; t < tiles; ++t) {
-            const int cnt = cursor[(size_t)t];
+        for (int64_t tile = 0; tile < t.count; ++tile) {
+            const int cnt = cursor[(size_t)tile];
             if (cnt == 0) continue;
-            ids[k] = (int)t; offs[k] = (int)at; ++k;
-            cursor[(size_t)t] = (int)at;
+            ids[k] = (int)tile; offs[k] = (int)at; ++k;
+            cursor[(size_t)tile] = (int)at;
             at += cnt;
         }
         offs[n_tiles] = (int)at;
@@ -2530,260 +2369,104 @@ int do_place(vt_volume* v, int n, const double* m4x4s, const double* weights, in
         }
     }
 
-    v->last_kernel = 17;
-    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-    v->last_lds[0] = Lmax[0]; v->last_lds[1] = Lmax[1]; v->last_lds[2] = Lmax[2];
-    v->last_lds_bytes = (int)lds_bytes; v->last_grid = (int)n_tiles;
+    record_launch(v, 17, t.T, dims.L, dims.lds_bytes, n_tiles);
     if (n_tiles == 0 && accumulate) return 0;          // nothing can land anywhere: `out` stays as found, nothing is launched
 
-    float* d_out = out;
-    PinnedScope pin(host_out ? out : nullptr, host_out ? n_out * sizeof(float) : 0);       // the caller's array: in (accumulate) and out
-    if (host_out) {
-        if ((rc = host_output_buffer(v, n_out, &d_out))) return rc;
-        if (accumulate) VT_HIP(pin.copy(d_out, out, n_out * sizeof(float), hipMemcpyHostToDevice, v->stream));
-    }
-    if (!accumulate) VT_HIP(hipMemsetAsync(d_out, 0, n_out * sizeof(float), v->stream));
+    ResultScope res(v, out, n_out * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open(accumulate))) return rc;
+    if (!accumulate) VT_HIP(hipMemsetAsync(res.ptr<float>(), 0, n_out * sizeof(float), v->stream));
     if (n_tiles > 0) {                                // (a grid of 0 is an error)
-        if (v->batch_m_cap < tab.size()) {
-            if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-            VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-            v->batch_m_cap = tab.size();
-        }
-        VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, v->stream));
+        if ((rc = upload_tables(v))) return rc;
         const int* d_ids = reinterpret_cast<const int*>(v->d_batch_m + ints_at);
-        VT_HIP(launch_place(cfg, v->interp, v->d_src, d_out, v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m),
-                            v->d_batch_m + per * (size_t)n, d_ids, d_ids + n_tiles, d_ids + 2 * n_tiles + 1, (int)n_tiles, accumulate, p,
-                            (int)lds_bytes, v->stream));
+        VT_HIP(launch_place(t.cfg, v->interp, v->d_src, res.ptr<float>(), v->d_zeros, device_entries(v), v->d_batch_m + kEntryDoubles * (size_t)n,
+                            d_ids, d_ids + n_tiles, d_ids + 2 * n_tiles + 1, (int)n_tiles, accumulate, p, dims.lds_bytes, v->stream));
     }
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+    return res.finish();
 }
 
 // One volume of shape (od, oh, ow) from the handle's planes taken as a stack of T images: n weighted 2-D samples per voxel, image
 // planes[i] at rows 1 and 2 of matrix i, summed in float64 in ascending order and rounded once -- do_place without the lists: kernel 18
 // (vt_kernels_backproject.hip) runs one workgroup per output tile over all n entries, so nothing is zeroed first.  The tile is do_place's,
-// the entries are do_place's for the matrix whose row 0 is (0, 0, 0, planes[i]); an entry stages into LDS when two patches of its size
-// fit (the kernel keeps the next entry's patch in flight while it samples).  Does not read or change the handle's own output shape.
+// the tables are build_backproject_tables' for one box.  Does not read or change the handle's own output shape.
 int do_backproject(vt_volume* v, int n, const double* m4x4s, const int32_t* planes, const double* weights, int od, int oh, int ow, float* out,
                    int flags)
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    if (od <= 0 || oh <= 0 || ow <= 0) return fail(VT_EINVAL, "non-positive output dims (%d,%d,%d)", od, oh, ow);
-    if ((int64_t)od * oh > 0x7fffffffLL || (int64_t)oh * ow > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large");
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "back-projection is available for whole-volume handles only (this one holds a slab window)");
-    if (is_filtered(v->interp) && !v->stack)
-        return fail(VT_EUNSUPPORTED, "the handle's coefficients are prefiltered along axis 0 as well: back-projection with a filt_* interpolation "
-                                     "needs in-plane coefficients (create the handle with VT_STACK)");
-    if (v->edge_pad) return fail(VT_EUNSUPPORTED, "back-projection is not available on VT_EDGE_SCIPY handles");
-    int rc = use_device(v->dev);
-    if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)n * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
-    if (weights)
-        for (int i = 0; i < n; ++i)
-            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %d is not finite", i);
-    if (planes) {
-        for (int i = 0; i < n; ++i)
-            if (planes[i] < 0 || planes[i] >= v->D) return fail(VT_EINVAL, "plane index %d of entry %d outside [0, %d)", planes[i], i, v->D);
-    } else if (n != v->D) {
-        return fail(VT_EINVAL, "%d matrices for a stack of %d images and no plane indices", n, v->D);
-    }
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_shape("output", od, oh, ow)) || (rc = check_backproject_handle(v)) || (rc = select_device(v)) ||
+        (rc = check_finite_matrices(m4x4s, (size_t)n)) || (rc = check_finite_weights(weights, (size_t)n)) ||
+        (rc = check_planes(v, n, planes, "")))
+        return rc;
 
-    const bool cubic = is_cubic(v->interp);
     const int shape[3] = {od, oh, ow};
     const size_t n_out = (size_t)od * oh * ow;
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
     const bool accumulate = (flags & VT_ACCUMULATE) != 0;
-    const int cfg = extract_pick_tile(cubic, shape, nullptr);      // a function of (output shape, interpolation): do_place's tile
-    int T[3];
-    extract_tile(cfg, &T[0], &T[1], &T[2]);
-    const int nT[3] = {(od + T[0] - 1) / T[0], (oh + T[1] - 1) / T[1], (ow + T[2] - 1) / T[2]};
-    const int64_t tiles = (int64_t)nT[0] * nT[1] * nT[2];
-    if (tiles > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large (%lld tiles)", (long long)tiles);
+    // a function of (output shape, interpolation): do_place's tile
+    const BoxTiles t = box_tiles(extract_pick_tile(is_cubic(v->interp), shape, nullptr), od, oh, ow);
+    if (t.count > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large (%lld tiles)", (long long)t.count);
 
-    // the launch's tables: one ExtractEntry per matrix, then the n weights
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    const size_t per = sizeof(ExtractEntry) / sizeof(double);
-    std::vector<double>& tab = v->h_batch_m;
-    tab.resize((size_t)n * (per + 1));
-    int Lmax[2] = {0, 0};
-    int64_t buf_floats = 4;
-    for (int i = 0; i < n; ++i) {
-        const double* a = m4x4s + 16 * (size_t)i;
-        double m[12] = {0, 0, 0, (double)(planes ? planes[i] : i), a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11]};
-        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * (size_t)i);
-        // tile reach, Q32.32 increments and patch dims by extract_box_dims' rule (no cap: the cap below is on two 2-D patches)
-        extract_fill_entry(m, cfg, cubic, 0x7fffffff, false, e);
-        const int64_t patch = (int64_t)e->Ly * e->Lx;
-        if (e->tiled && !force_direct && 2 * patch * 4 <= (int64_t)v->lds_limit) {
-            if (patch > buf_floats || Lmax[0] == 0) { Lmax[0] = e->Ly; Lmax[1] = e->Lx; }      // the largest staged patch
-            buf_floats = std::max(buf_floats, patch);
-        } else {
-            e->tiled = 0;
-        }
-        tab[per * (size_t)n + (size_t)i] = weights ? weights[i] : 1.0;
-    }
-    const int lds_bytes = (int)(2 * buf_floats * 4);
-    AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    TilePlan plan;
-    {
-        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, od, oh, ow, true);
-        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, output dims, valid interval
-    }
-    p.nTd = nT[0]; p.nTh = nT[1]; p.nTw = nT[2];
+    TableDims dims;
+    int buf_floats = 0;
+    if ((rc = build_backproject_tables(v, m4x4s, 1, n, planes, weights, t.cfg, force_direct, &dims, &buf_floats))) return rc;
+    const AffineParams p = box_params(v, od, oh, ow, t.nT);
+    record_launch(v, 18, t.T, dims.L, dims.lds_bytes, t.count);
 
-    v->last_kernel = 18;
-    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-    v->last_lds[0] = 2; v->last_lds[1] = Lmax[0]; v->last_lds[2] = Lmax[1];
-    v->last_lds_bytes = lds_bytes; v->last_grid = (int)tiles;
-
-    float* d_out = out;
-    PinnedScope pin(host_out ? out : nullptr, host_out ? n_out * sizeof(float) : 0);       // the caller's array: in (accumulate) and out
-    if (host_out) {
-        if ((rc = host_output_buffer(v, n_out, &d_out))) return rc;
-        if (accumulate) VT_HIP(pin.copy(d_out, out, n_out * sizeof(float), hipMemcpyHostToDevice, v->stream));
-    }
-    if (v->batch_m_cap < tab.size()) {
-        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-        v->batch_m_cap = tab.size();
-    }
-    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                               hipMemcpyHostToDevice, v->stream));
-    VT_HIP(launch_backproject(cfg, v->interp, v->d_src, d_out, v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m),
-                              v->d_batch_m + per * (size_t)n, n, (int)buf_floats, accumulate, p, lds_bytes, v->stream));
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+    ResultScope res(v, out, n_out * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open(accumulate)) || (rc = upload_tables(v))) return rc;
+    VT_HIP(launch_backproject(t.cfg, v->interp, v->d_src, res.ptr<float>(), v->d_zeros, device_entries(v), v->d_batch_m + kEntryDoubles * (size_t)n,
+                              n, buf_floats, accumulate, p, dims.lds_bytes, v->stream));
+    return res.finish();
 }
 
 // nb boxes of one shape (bd, bh, bw) from the handle's stack, n entries per box: box b is what do_backproject writes for matrices
-// m4x4s + 16 n b, the shared planes and weights + n b at that output shape, bit for bit -- the same tile, the same entry through
-// extract_fill_entry, the same per-entry staging decision (two patches of ITS size within lds_limit; the batch-wide largest patch only
-// sizes the allocation and places the second buffer) and kernel 18's text with a box index (kernel 19, vt_kernels_backprojectboxes.hip):
-// one launch of nb x tiles workgroups instead of nb launches, syncs and uploads.  Tables: nb x n entries, then nb x n weights.
-// MT: float or double matrices, widened entry by entry (no nb x n x 16 float64 copy of a float32 batch).
+// m4x4s + 16 n b, the shared planes and weights + n b at that output shape, bit for bit -- the same tile, the same tables
+// (build_backproject_tables) and kernel 18's text with a box index (kernel 19, vt_kernels_backprojectboxes.hip): one launch of nb x tiles
+// workgroups instead of nb launches, syncs and uploads.  MT: float or double matrices.
 template <typename MT>
 int do_backproject_boxes(vt_volume* v, int nb, int n, const MT* m4x4s, const int32_t* planes, const double* weights, int bd, int bh,
                          int bw, float* out, int flags)
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (nb <= 0) return fail(VT_EINVAL, "number of boxes %d", nb);
-    if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    if (bd <= 0 || bh <= 0 || bw <= 0) return fail(VT_EINVAL, "non-positive box dims (%d,%d,%d)", bd, bh, bw);
-    if ((int64_t)bd * bh > 0x7fffffffLL || (int64_t)bh * bw > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "box too large");
-    if (v->deferred) return fail(VT_EINVAL, "handle has not been finalized (vt_volume_finalize)");
-    if (v->plane0 != 0 || v->gD != v->D || v->out_plane0 != 0)
-        return fail(VT_EINVAL, "back-projection is available for whole-volume handles only (this one holds a slab window)");
-    if (is_filtered(v->interp) && !v->stack)
-        return fail(VT_EUNSUPPORTED, "the handle's coefficients are prefiltered along axis 0 as well: back-projection with a filt_* interpolation "
-                                     "needs in-plane coefficients (create the handle with VT_STACK)");
-    if (v->edge_pad) return fail(VT_EUNSUPPORTED, "back-projection is not available on VT_EDGE_SCIPY handles");
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_shape("box", bd, bh, bw)) || (rc = check_backproject_handle(v))) return rc;
     // the bounds, before anything of the caller's arrays is read
     const int64_t total = (int64_t)nb * n;                // entries of the call
     if (total > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "%d boxes x %d entries: more than 2^31 - 1 (box, entry) pairs", nb, n);
-    const bool cubic = is_cubic(v->interp);
     const int shape[3] = {bd, bh, bw};
     const size_t box_vox = (size_t)bd * bh * bw;          // < 2^62 by the checks above
     if (box_vox > (SIZE_MAX / sizeof(float)) / (size_t)nb) return fail(VT_EUNSUPPORTED, "output too large (%d boxes)", nb);
-    const size_t n_out = box_vox * (size_t)nb;
-    const int cfg = extract_pick_tile(cubic, shape, nullptr);      // a function of (box shape, interpolation): do_backproject's tile
-    int T[3];
-    extract_tile(cfg, &T[0], &T[1], &T[2]);
-    const int nT[3] = {(bd + T[0] - 1) / T[0], (bh + T[1] - 1) / T[1], (bw + T[2] - 1) / T[2]};
-    const int64_t tiles = (int64_t)nT[0] * nT[1] * nT[2];
-    if (tiles > 0x7fffffffLL || tiles * nb > 0x7fffffffLL)
-        return fail(VT_EUNSUPPORTED, "grid too large (%d boxes x %lld tiles)", nb, (long long)tiles);
-    int rc = use_device(v->dev);
-    if (rc) return rc;
-    (void)hipGetLastError();
-    for (size_t i = 0; i < (size_t)total * 16; ++i)
-        if (!std::isfinite(m4x4s[i])) return fail(VT_EINVAL, "matrix %zu entry %zu is not finite", i / 16, i % 16);
-    if (weights)
-        for (size_t i = 0; i < (size_t)total; ++i)
-            if (!std::isfinite(weights[i])) return fail(VT_EINVAL, "weight %zu is not finite", i);
-    if (planes) {
-        for (int i = 0; i < n; ++i)
-            if (planes[i] < 0 || planes[i] >= v->D) return fail(VT_EINVAL, "plane index %d of entry %d outside [0, %d)", planes[i], i, v->D);
-    } else if (n != v->D) {
-        return fail(VT_EINVAL, "%d matrices per box for a stack of %d images and no plane indices", n, v->D);
-    }
+    // a function of (box shape, interpolation): do_backproject's tile
+    const BoxTiles t = box_tiles(extract_pick_tile(is_cubic(v->interp), shape, nullptr), bd, bh, bw);
+    if (t.count > 0x7fffffffLL || t.count * nb > 0x7fffffffLL)
+        return fail(VT_EUNSUPPORTED, "grid too large (%d boxes x %lld tiles)", nb, (long long)t.count);
+    if ((rc = select_device(v)) || (rc = check_finite_matrices(m4x4s, (size_t)total)) || (rc = check_finite_weights(weights, (size_t)total)) ||
+        (rc = check_planes(v, n, planes, " per box")))
+        return rc;
 
-    const bool host_out = !(flags & VT_OUT_DEVICE);
     const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
     const bool accumulate = (flags & VT_ACCUMULATE) != 0;
 
-    // the launch's tables: one ExtractEntry per (box, entry), then the nb x n weights; 200 bytes per pair, < 2^31 pairs: no overflow
-    VT_HIP(hipStreamSynchronize(v->stream));          // the previous batch may still be reading the staging vector
-    const size_t per = sizeof(ExtractEntry) / sizeof(double);
-    std::vector<double>& tab = v->h_batch_m;
-    tab.resize((size_t)total * (per + 1));
-    int Lmax[2] = {0, 0};
-    int64_t buf_floats = 4;
-    for (size_t k = 0; k < (size_t)total; ++k) {
-        const MT* a = m4x4s + 16 * k;
-        const int i = (int)(k % (size_t)n);
-        double m[12] = {0, 0, 0, (double)(planes ? planes[i] : i), (double)a[4], (double)a[5], (double)a[6], (double)a[7], (double)a[8],
-                        (double)a[9], (double)a[10], (double)a[11]};
-        ExtractEntry* e = reinterpret_cast<ExtractEntry*>(tab.data() + per * k);
-        extract_fill_entry(m, cfg, cubic, 0x7fffffff, false, e);      // as in do_backproject
-        const int64_t patch = (int64_t)e->Ly * e->Lx;
-        // staged or not: this entry and lds_limit alone, do_backproject's rule, whatever the rest of the batch holds
-        if (e->tiled && !force_direct && 2 * patch * 4 <= (int64_t)v->lds_limit) {
-            if (patch > buf_floats || Lmax[0] == 0) { Lmax[0] = e->Ly; Lmax[1] = e->Lx; }      // the largest staged patch
-            buf_floats = std::max(buf_floats, patch);
-        } else {
-            e->tiled = 0;
-        }
-        tab[per * (size_t)total + k] = weights ? weights[k] : 1.0;
-    }
-    const int lds_bytes = (int)(2 * buf_floats * 4);
-    AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    TilePlan plan;
-    {
-        const vt_volume view = planning_view(v, v->D, v->H, v->W, v->P, bd, bh, bw, true);
-        plan_launch(&view, tab.data(), VT_FORCE_DIRECT, &p, &plan);      // source dims, box dims, valid interval
-    }
-    p.nTd = nT[0]; p.nTh = nT[1]; p.nTw = nT[2];
+    TableDims dims;
+    int buf_floats = 0;
+    if ((rc = build_backproject_tables(v, m4x4s, nb, n, planes, weights, t.cfg, force_direct, &dims, &buf_floats))) return rc;
+    const AffineParams p = box_params(v, bd, bh, bw, t.nT);
+    record_launch(v, 19, t.T, dims.L, dims.lds_bytes, t.count * nb);
 
-    v->last_kernel = 19;
-    v->last_tile[0] = T[0]; v->last_tile[1] = T[1]; v->last_tile[2] = T[2];
-    v->last_lds[0] = 2; v->last_lds[1] = Lmax[0]; v->last_lds[2] = Lmax[1];
-    v->last_lds_bytes = lds_bytes; v->last_grid = (int)(tiles * nb);
+    ResultScope res(v, out, box_vox * (size_t)nb * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open(accumulate)) || (rc = upload_tables(v))) return rc;
+    VT_HIP(launch_backproject_boxes(t.cfg, v->interp, v->d_src, res.ptr<float>(), v->d_zeros, device_entries(v),
+                                    v->d_batch_m + kEntryDoubles * (size_t)total, nb, n, buf_floats, accumulate, p, dims.lds_bytes, v->stream));
+    return res.finish();
+}
 
-    float* d_out = out;
-    PinnedScope pin(host_out ? out : nullptr, host_out ? n_out * sizeof(float) : 0);       // the caller's array: in (accumulate) and out
-    if (host_out) {
-        if ((rc = host_output_buffer(v, n_out, &d_out))) return rc;
-        if (accumulate) VT_HIP(pin.copy(d_out, out, n_out * sizeof(float), hipMemcpyHostToDevice, v->stream));
-    }
-    if (v->batch_m_cap < tab.size()) {
-        if (v->d_batch_m) { VT_HIP(hipFree(v->d_batch_m)); v->d_batch_m = nullptr; v->batch_m_cap = 0; }
-        VT_HIP(hipMalloc(reinterpret_cast<void**>(&v->d_batch_m), tab.size() * sizeof(double)));
-        v->batch_m_cap = tab.size();
-    }
-    VT_HIP(PinnedScope::sliced(reinterpret_cast<char*>(v->d_batch_m), reinterpret_cast<const char*>(tab.data()), tab.size() * sizeof(double),
-                               hipMemcpyHostToDevice, v->stream));
-    VT_HIP(launch_backproject_boxes(cfg, v->interp, v->d_src, d_out, v->d_zeros, reinterpret_cast<const ExtractEntry*>(v->d_batch_m),
-                                    v->d_batch_m + per * (size_t)total, nb, n, (int)buf_floats, accumulate, p, lds_bytes, v->stream));
-    if (host_out) {
-        VT_HIP(pin.copy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, v->stream));
-        VT_HIP(hipStreamSynchronize(v->stream));
-    }
-    return 0;
+// a float32 batch of n matrices in float64
+std::vector<double> widened(const float* m4x4s, int n)
+{
+    std::vector<double> m((size_t)n * 16);
+    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
+    return m;
 }
 
 }  // namespace
@@ -3111,17 +2794,13 @@ int vt_volume_affine_f64(vt_volume_t* v, const double* m4x4, float* out, int fla
 int vt_volume_affine_batch(vt_volume_t* v, int n, const float* m4x4s, float* out, int flags)
 {
     if (!m4x4s || n <= 0) return fail(VT_EINVAL, "NULL matrices or empty batch");
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_affine_batch(v, n, m.data(), out, flags);
+    return do_affine_batch(v, n, widened(m4x4s, n).data(), out, flags);
 }
 
 int vt_volume_extract(vt_volume_t* v, int n, const float* m4x4s, int box_d, int box_h, int box_w, float* out, int flags)
 {
     if (!v || !m4x4s || !out || n <= 0) return fail(VT_EINVAL, "NULL argument or empty batch");
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_extract(v, n, m.data(), box_d, box_h, box_w, out, flags);
+    return do_extract(v, n, widened(m4x4s, n).data(), box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_extract_f64(vt_volume_t* v, int n, const double* m4x4s, int box_d, int box_h, int box_w, float* out, int flags)
@@ -3134,9 +2813,7 @@ int vt_volume_extract_sum(vt_volume_t* v, int n, const float* m4x4s, const doubl
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_extract_sum(v, n, m.data(), weights, box_d, box_h, box_w, out, flags);
+    return do_extract_sum(v, n, widened(m4x4s, n).data(), weights, box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_extract_sum_f64(vt_volume_t* v, int n, const double* m4x4s, const double* weights, int box_d, int box_h, int box_w, float* out,
@@ -3150,9 +2827,7 @@ int vt_volume_extract_sum_multi(vt_volume_t* v, int n, const float* m4x4s, int g
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_extract_sum_multi(v, n, m.data(), g, weights, box_d, box_h, box_w, out, flags);
+    return do_extract_sum_multi(v, n, widened(m4x4s, n).data(), g, weights, box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_extract_sum_multi_f64(vt_volume_t* v, int n, const double* m4x4s, int g, const double* weights, int box_d, int box_h, int box_w,
@@ -3165,9 +2840,7 @@ int vt_volume_place(vt_volume_t* v, int n, const float* m4x4s, const double* wei
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_place(v, n, m.data(), weights, out_d, out_h, out_w, out, flags);
+    return do_place(v, n, widened(m4x4s, n).data(), weights, out_d, out_h, out_w, out, flags);
 }
 
 int vt_volume_place_f64(vt_volume_t* v, int n, const double* m4x4s, const double* weights, int out_d, int out_h, int out_w, float* out,
@@ -3181,9 +2854,7 @@ int vt_volume_backproject(vt_volume_t* v, int n, const float* m4x4s, const int32
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_backproject(v, n, m.data(), planes, weights, out_d, out_h, out_w, out, flags);
+    return do_backproject(v, n, widened(m4x4s, n).data(), planes, weights, out_d, out_h, out_w, out, flags);
 }
 
 int vt_volume_backproject_f64(vt_volume_t* v, int n, const double* m4x4s, const int32_t* planes, const double* weights, int out_d, int out_h,
@@ -3209,9 +2880,7 @@ int vt_volume_extract_dot(vt_volume_t* v, int n, const float* m4x4s, const float
 {
     if (!v || !m4x4s || !tmpl || !out) return fail(VT_EINVAL, "NULL argument");
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_extract_dot(v, n, m.data(), tmpl, mask, box_d, box_h, box_w, out, flags);
+    return do_extract_dot(v, n, widened(m4x4s, n).data(), tmpl, mask, box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_extract_dot_f64(vt_volume_t* v, int n, const double* m4x4s, const float* tmpl, const float* mask, int box_d, int box_h, int box_w,
@@ -3225,9 +2894,7 @@ int vt_volume_extract_dot_multi(vt_volume_t* v, int n, const float* m4x4s, int k
 {
     if (!v || !m4x4s || !tmpls || !out) return fail(VT_EINVAL, "NULL argument");
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_extract_dot_multi(v, n, m.data(), k, tmpls, mask, box_d, box_h, box_w, out, flags);
+    return do_extract_dot_multi(v, n, widened(m4x4s, n).data(), k, tmpls, mask, box_d, box_h, box_w, out, flags);
 }
 
 int vt_volume_extract_dot_multi_f64(vt_volume_t* v, int n, const double* m4x4s, int k, const float* tmpls, const float* mask, int box_d,
@@ -3253,9 +2920,7 @@ int vt_volume_project_batch(vt_volume_t* v, int n, const float* m4x4s, int depth
 {
     if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
     if (n <= 0) return fail(VT_EINVAL, "batch size %d", n);
-    std::vector<double> m((size_t)n * 16);
-    for (size_t i = 0; i < m.size(); ++i) m[i] = (double)m4x4s[i];
-    return do_project_batch(v, n, m.data(), depth, height, width, out, flags);
+    return do_project_batch(v, n, widened(m4x4s, n).data(), depth, height, width, out, flags);
 }
 
 int vt_volume_project_batch_f64(vt_volume_t* v, int n, const double* m4x4s, int depth, int height, int width, float* out, int flags)
