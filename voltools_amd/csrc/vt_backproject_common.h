@@ -7,20 +7,14 @@
 // compiled with the same flags, which is what makes a box of kind 19 the bits of kind 18's volume for that box's matrices.  The body is
 // kept inside the __global__ function: moved into a __device__ function called from two kernels, the same text took up to 29 more
 // VGPRs in kind 18's instantiations.
+//
+// Thread mapping, tile decode and weighted_add are the box family's (vt_box_common.h).  The geometry is not: patch_geo works on rows 1
+// and 2 only and returns before anything else is formed when the tile misses the image; the family's three-row form would add a row
+// this kernel never reads.
 #pragma once
-#include "vt_internal.h"
-#include "vt_device.h"
+#include "vt_box_common.h"
 
 namespace vt {
-
-// acc + w * v in float64: extract_sum_tiled's / place_tiled's weighted_add, text and compile flags, so that the kernels assemble to the
-// same instructions (the translation unit is compiled with -ffp-contract=fast)
-__device__ __forceinline__ double backproject_weighted_add(double acc, double w, float v)
-{
-#pragma clang fp contract(off)
-    const double t = w * (double)v;
-    return acc + t;
-}
 
 // wave-uniform geometry of one entry on one tile: rows 1 and 2 only
 struct PatchGeo {
@@ -172,13 +166,8 @@ __global__ __launch_bounds__(256) void backproject_tiled(const float* __restrict
                                                           const double* __restrict__ wts, const int n, const int buf_floats,
                                                           const int accumulate, const int tiles, const AffineParams p)
 {
-    constexpr int NPOS = TH * TW;
-    static_assert(256 % TW == 0 && (NPOS >= 256 ? NPOS % 256 == 0 : 256 % NPOS == 0), "tile/thread mapping");
-    constexpr int DG = NPOS >= 256 ? 1 : 256 / NPOS;     // depth groups
-    constexpr int NJ = NPOS >= 256 ? NPOS / 256 : 1;     // in-plane passes
-    constexpr int RP = NPOS >= 256 ? 256 / TW : TH;      // tile rows covered per pass
-    constexpr int DPT = TD / DG;                         // planes per thread
-    static_assert(TD % DG == 0, "tile depth / lane groups");
+    using M = BoxTileMap<TD, TH, TW>;
+    constexpr int NJ = M::NJ, RP = M::RP, DPT = M::DPT;
     constexpr bool CUBIC = KIND != 0;
     constexpr int HALO = CUBIC ? 1 : 0;
     constexpr int UNR = CUBIC ? 2 : 4;                   // samples in flight (place_tiled's)
@@ -195,18 +184,13 @@ __global__ __launch_bounds__(256) void backproject_tiled(const float* __restrict
         wts += (int64_t)b * n;
         out += (int64_t)b * ((int64_t)p.oD * p.oH * p.oW);
     }
-    const int tw_i = u % p.nTw;
-    const int u2 = u / p.nTw;
-    const int th_i = u2 % p.nTh;
-    const int td_i = u2 / p.nTh;
-    const int d0 = td_i * TD, h0 = th_i * TH, w0 = tw_i * TW;
+    int d0, h0, w0;
+    M::tile_origin(u, p, d0, h0, w0);
     const int64_t ostride = (int64_t)p.oH * p.oW;
     const int64_t istride = (int64_t)p.sH * p.sP;        // floats between the images of the stack
 
-    const int pos = DG > 1 ? tid % NPOS : tid;
-    const int kw = pos % TW;
-    const int jh0 = pos / TW;
-    const int i0 = DG > 1 ? (tid / NPOS) * DPT : 0;
+    int kw, jh0, i0;
+    M::thread_origin(tid, kw, jh0, i0);
     const int nd = min(DPT, p.oD - d0 - i0);             // planes this thread owns (<= 0: none)
 
     double acc[NJ * DPT];                                // statically indexed throughout: registers
@@ -261,7 +245,7 @@ __global__ __launch_bounds__(256) void backproject_tiled(const float* __restrict
                         const double s2 = fma(e.m[8], (double)d, fma(e.m[9], (double)h, fma(e.m[10], (double)w, e.m[11])));
                         if ((s1 >= p.vlo[1]) && (s1 < p.vhi[1]) && (s2 >= p.vlo[2]) && (s2 < p.vhi[2])) {
                             const double fyd = floor(s1), fxd = floor(s2);
-                            a = backproject_weighted_add(a, wt, direct_sample_2d<KIND>(img, p, (int)fyd, (int)fxd, (float)(s1 - fyd),
+                            a = weighted_add(a, wt, direct_sample_2d<KIND>(img, p, (int)fyd, (int)fxd, (float)(s1 - fyd),
                                                                                        (float)(s2 - fxd)));
                         }
                     }
@@ -316,7 +300,7 @@ __global__ __launch_bounds__(256) void backproject_tiled(const float* __restrict
                         inside = (ib + k < nd) && (t1 >= p.vlo[1]) && (t1 < p.vhi[1]) && (t2 >= p.vlo[2]) && (t2 < p.vhi[2]);
                     }
                     const float val = sample_patch<KIND>(buf, Lx, c1.hi, c2.hi, fx_frac(c1), fx_frac(c2));
-                    a[k] = inside ? backproject_weighted_add(acc[jj * DPT + k], wt, val) : acc[jj * DPT + k];
+                    a[k] = inside ? weighted_add(acc[jj * DPT + k], wt, val) : acc[jj * DPT + k];
                     fx_step(c1, inc_hi1, inc_lo1);
                     fx_step(c2, inc_hi2, inc_lo2);
                 }

@@ -37,37 +37,7 @@ namespace vt {
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-typedef void (*backproject_fn)(const float*, float*, const float*, const ExtractEntry*, const double*, int, int, int, int, const AffineParams);
-
-template <int TD, int TH, int TW>
-static backproject_fn pick_backproject(int kind)
-{
-    switch (kind) {
-        case 0: return backproject_tiled<0, TD, TH, TW, false>;
-        case 1: return backproject_tiled<1, TD, TH, TW, false>;
-        default: return backproject_tiled<2, TD, TH, TW, false>;
-    }
-}
-
-static backproject_fn backproject_entry_point(int cfg, int kind)      // the extraction kernel's tile table (extract_tile)
-{
-    switch (cfg) {
-        case 0: return pick_backproject<16, 16, 16>(kind);
-        case 1: return pick_backproject<8, 16, 16>(kind);
-        default: return pick_backproject<8, 8, 16>(kind);
-    }
-}
-
-hipError_t init_backproject_kernels()
-{
-    for (int cfg = 0; cfg < extract_tile_count(); ++cfg)
-        for (int kind = 0; kind < 3; ++kind) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(backproject_entry_point(cfg, kind)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
+VT_BOX_KERNELS(backproject, backproject_tiled<KIND, T::TD, T::TH, T::TW, false>)
 
 // grid = p.nTd * nTh * nTw workgroups.  lds_bytes >= 2 * buf_floats * 4; every tiled entry's Ly * Lx <= buf_floats.
 hipError_t launch_backproject(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
@@ -77,7 +47,7 @@ hipError_t launch_backproject(int cfg, int interp, const float* src, float* out,
     const int64_t grid = (int64_t)p.nTd * p.nTh * p.nTw;
     if (n <= 0 || grid <= 0 || grid > 0x7fffffffLL || buf_floats < 0 || (buf_floats & 3) || (int64_t)buf_floats * 8 > lds_bytes)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(backproject_entry_point(cfg, interp_kind(interp)), dim3((unsigned)grid), dim3(256), lds_bytes, stream,
+    hipLaunchKernelGGL(backproject_kernels.fn[cfg][interp_kind(interp)], dim3((unsigned)grid), dim3(256), lds_bytes, stream,
                        src, out, zeros16, d_tab, d_wts, n, buf_floats, accumulate ? 1 : 0, 0, p);
     return hipGetLastError();
 }

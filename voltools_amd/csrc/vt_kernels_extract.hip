@@ -7,9 +7,10 @@
 //   * One 256-thread workgroup per (matrix, box tile) pair.  The host uploads one table entry per matrix (ExtractEntry:
 //     the folded 3x4 matrix, the tile reach, the Q32.32 depth steps, the staged box dims); the workgroup reads its entry
 //     with scalar loads, so everything per-matrix lives in SGPRs exactly as the kernarg block does for affine_tiled.
-//   * Geometry, staging and gather are affine_tiled's: float64 tile bounding box, stage_box (16-byte direct-to-LDS
-//     loads, zero vector outside the volume), sample_box<KIND> (same weights, same association), canonical float64
-//     inside test on tiles cut by the valid interval or by the end of the box.
+//   * Thread mapping, float64 tile bounding box, staged-box origin, canonical float64 inside test (tiles cut by the valid
+//     interval or by the end of the box) and Q32.32 stepping are the box family's, written once in vt_box_common.h for
+//     kinds 11-19.  Staging and gather are affine_tiled's: stage_box (16-byte direct-to-LDS loads, zero vector outside
+//     the volume), sample_box<KIND> (same weights, same association).
 //   * Box i is a function of its own entry only.  The tile shape -- it fixes where the fixed-point stepping restarts,
 //     hence last bits -- comes from (box shape, interpolation); whether an entry stages into LDS or gathers from global
 //     memory comes from its own footprint against a fixed cap.  Nothing depends on the batch: the LDS strides are per
@@ -18,8 +19,7 @@
 //     same launch, with the arithmetic of affine_direct: same output order, no second launch.
 //   * Workgroup ids are XCD-contiguous and box-major: the tiles of one box are neighbours on one XCD, so the halves
 //     of the staged boxes that adjacent tiles of a rotated box share can hit that XCD's L2.
-#include "vt_internal.h"
-#include "vt_device.h"
+#include "vt_box_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,14 +32,8 @@ __global__ __launch_bounds__(256) void extract_tiled(const float* __restrict__ s
                                                       const float* __restrict__ zeros16,
                                                       const ExtractEntry* __restrict__ tab, const AffineParams p)
 {
-    // lanes run along w, then h; tiles of fewer than 256 in-plane positions split their depth between lane groups
-    constexpr int NPOS = TH * TW;
-    static_assert(256 % TW == 0 && (NPOS >= 256 ? NPOS % 256 == 0 : 256 % NPOS == 0), "tile/thread mapping");
-    constexpr int DG = NPOS >= 256 ? 1 : 256 / NPOS;     // depth groups
-    constexpr int NJ = NPOS >= 256 ? NPOS / 256 : 1;     // in-plane passes
-    constexpr int RP = NPOS >= 256 ? 256 / TW : TH;      // tile rows covered per pass
-    constexpr int DPT = TD / DG;                         // planes per thread
-    static_assert(TD % DG == 0, "tile depth / lane groups");
+    using M = BoxTileMap<TD, TH, TW>;
+    constexpr int NJ = M::NJ, RP = M::RP, DPT = M::DPT;
     constexpr bool CUBIC = KIND != 0;
     constexpr int HALO = CUBIC ? 1 : 0;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -48,20 +42,14 @@ __global__ __launch_bounds__(256) void extract_tiled(const float* __restrict__ s
     const int t = xcd_contiguous(blockIdx.x, gridDim.x);
     const int tiles = p.nTd * p.nTh * p.nTw;
     const int box = t / tiles;                           // wave-uniform: the entry is read with scalar loads
-    const int u = t - box * tiles;
-    const int tw_i = u % p.nTw;
-    const int u2 = u / p.nTw;
-    const int th_i = u2 % p.nTh;
-    const int td_i = u2 / p.nTh;
-    const int d0 = td_i * TD, h0 = th_i * TH, w0 = tw_i * TW;
+    int d0, h0, w0;
+    M::tile_origin(t - box * tiles, p, d0, h0, w0);
     const ExtractEntry& e = tab[box];
     const int64_t ostride = (int64_t)p.oH * p.oW;
     out += (int64_t)box * p.oD * ostride;
 
-    const int pos = DG > 1 ? tid % NPOS : tid;
-    const int kw = pos % TW;
-    const int jh0 = pos / TW;
-    const int i0 = DG > 1 ? (tid / NPOS) * DPT : 0;
+    int kw, jh0, i0;
+    M::thread_origin(tid, kw, jh0, i0);
     const int nd = min(DPT, p.oD - d0 - i0);             // planes this thread owns (<= 0: none)
 
     if (!e.tiled) {
@@ -75,11 +63,7 @@ __global__ __launch_bounds__(256) void extract_tiled(const float* __restrict__ s
                 const int d = d0 + i0 + i;
                 double s[3];
                 bool inside = true;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    s[r] = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                    inside = inside && (s[r] >= p.vlo[r]) && (s[r] < p.vhi[r]);
-                }
+                VT_CANONICAL_INSIDE(inside, s[r_], e, p, d, h, w);
                 float val = 0.0f;
                 if (inside) {
                     const double fzd = floor(s[0]), fyd = floor(s[1]), fxd = floor(s[2]);
@@ -91,17 +75,9 @@ __global__ __launch_bounds__(256) void extract_tiled(const float* __restrict__ s
         return;
     }
 
-    // ---- tile geometry (wave-uniform, float64), as affine_tiled ----
-    double base[3], lo[3], hi[3];
+    double base[3], lo[3];
     bool any_valid = true, all_valid = true;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        base[r] = fma(e.m[4 * r], (double)d0, fma(e.m[4 * r + 1], (double)h0, fma(e.m[4 * r + 2], (double)w0, e.m[4 * r + 3])));
-        lo[r] = base[r] + e.neg[r];
-        hi[r] = base[r] + e.pos[r];
-        any_valid = any_valid && (hi[r] >= p.vlo[r] - kTileMargin) && (lo[r] < p.vhi[r] + kTileMargin);
-        all_valid = all_valid && (lo[r] >= p.vlo[r] + kTileMargin) && (hi[r] < p.vhi[r] - kTileMargin);
-    }
+    VT_BOX_TILE_GEOMETRY(base, lo, any_valid, all_valid, e, p, d0, h0, w0);
 
     if (!any_valid) {
         // the whole tile maps outside the valid interval
@@ -116,22 +92,17 @@ __global__ __launch_bounds__(256) void extract_tiled(const float* __restrict__ s
         return;
     }
 
-    // integer origin of the staged box (finite and small: the tile meets the valid interval, its extent was bounded on the host)
     int o[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;     // (vt_device.h: kBoxMargin)
-    o[2] &= ~3;
+    box_origin<HALO>(lo, o);
 
     const int Lx = e.Lx, Ly = e.Ly, Lz = e.Lz;
     stage_box(lds, src, zeros16, p, o, Lz, Ly, Lx, tid);
     __syncthreads();     // hipcc drains the direct-to-LDS loads (vmcnt(0)) ahead of the barrier
 
     double b[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) b[r] = base[r] - (double)o[r];
+    box_base(base, o, b);
     const int LyLx = Ly * Lx;
-    const int inc_hi0 = e.inc_hi[0], inc_hi1 = e.inc_hi[1], inc_hi2 = e.inc_hi[2];
-    const unsigned inc_lo0 = e.inc_lo[0], inc_lo1 = e.inc_lo[1], inc_lo2 = e.inc_lo[2];
+    const FxInc3 inc = fx_inc3(e);
     const bool whole = all_valid && (p.oD - d0 >= TD);   // wave-uniform
 
 #pragma unroll
@@ -139,35 +110,26 @@ __global__ __launch_bounds__(256) void extract_tiled(const float* __restrict__ s
         const int j = jh0 + jj * RP;
         const int h = h0 + j, w = w0 + kw;
         if (h >= p.oH || w >= p.oW) continue;
-        const double s0 = fma(e.m[0], (double)i0, fma(e.m[1], (double)j, fma(e.m[2], (double)kw, b[0])));
-        const double s1 = fma(e.m[4], (double)i0, fma(e.m[5], (double)j, fma(e.m[6], (double)kw, b[1])));
-        const double s2 = fma(e.m[8], (double)i0, fma(e.m[9], (double)j, fma(e.m[10], (double)kw, b[2])));
-        Fx c0 = to_fx(s0), c1 = to_fx(s1), c2 = to_fx(s2);
+        Fx c0, c1, c2;
+        fx_start3(e, b, i0, j, kw, c0, c1, c2);
         float* optr = out + ((int64_t)(d0 + i0) * p.oH + h) * p.oW + w;
         if (whole) {
 #pragma unroll 4
             for (int i = 0; i < DPT; ++i) {
                 optr[i * ostride] = sample_box<KIND>(lds, Lx, LyLx, c0.hi, c1.hi, c2.hi, fx_frac(c0), fx_frac(c1), fx_frac(c2));
-                fx_step(c0, inc_hi0, inc_lo0);
-                fx_step(c1, inc_hi1, inc_lo1);
-                fx_step(c2, inc_hi2, inc_lo2);
+                fx_step3(c0, c1, c2, inc);
             }
         } else {
-            // tiles cut by the valid interval or by the end of the box: the inside test is the canonical float64 chain
-            // (affine_direct's and the oracle's), the taps still come from the fixed-point split
+            // tiles cut by the valid interval or by the end of the box: the inside test is the canonical chain, the taps still come
+            // from the fixed-point split
             for (int i = 0; i < nd; ++i) {
                 const int d = d0 + i0 + i;
+                double s;
                 bool inside = true;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const double s = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                    inside = inside && (s >= p.vlo[r]) && (s < p.vhi[r]);
-                }
+                VT_CANONICAL_INSIDE(inside, s, e, p, d, h, w);
                 const float val = sample_box<KIND>(lds, Lx, LyLx, c0.hi, c1.hi, c2.hi, fx_frac(c0), fx_frac(c1), fx_frac(c2));
                 optr[i * ostride] = inside ? val : 0.0f;
-                fx_step(c0, inc_hi0, inc_lo0);
-                fx_step(c1, inc_hi1, inc_lo1);
-                fx_step(c2, inc_hi2, inc_lo2);
+                fx_step3(c0, c1, c2, inc);
             }
         }
     }
@@ -176,14 +138,7 @@ __global__ __launch_bounds__(256) void extract_tiled(const float* __restrict__ s
 // ---------------------------------------------------------------------------------------------------
 // host side: tile table, per-entry planning, launcher
 // ---------------------------------------------------------------------------------------------------
-struct ExtractTile { int td, th, tw; };
-static const ExtractTile kExtractTiles[] = {
-    {16, 16, 16},   // 0: cube -- fewest staged bytes per voxel, one workgroup per CU under a general rotation
-    {8, 16, 16},    // 1: half cube
-    {8, 8, 16},     // 2: quarter cube -- a general cubic rotation stages under 40 KiB
-};
-
-int extract_tile_count() { return (int)(sizeof(kExtractTiles) / sizeof(kExtractTiles[0])); }
+int extract_tile_count() { return kExtractTileCount; }
 void extract_tile(int idx, int* td, int* th, int* tw) { *td = kExtractTiles[idx].td; *th = kExtractTiles[idx].th; *tw = kExtractTiles[idx].tw; }
 
 // Staged box of tile T under matrix m (pick_box_tile's formula): false when the extent is absurd.
@@ -250,43 +205,13 @@ void extract_fill_entry(const double m[12], int cfg, bool cubic, int lds_cap, bo
     }
 }
 
-typedef void (*extract_fn)(const float*, float*, const float*, const ExtractEntry*, const AffineParams);
-
-template <int TD, int TH, int TW>
-static extract_fn pick_extract(int kind)
-{
-    switch (kind) {
-        case 0: return extract_tiled<0, TD, TH, TW>;
-        case 1: return extract_tiled<1, TD, TH, TW>;
-        default: return extract_tiled<2, TD, TH, TW>;
-    }
-}
-
-static extract_fn extract_entry_point(int cfg, int kind)
-{
-    switch (cfg) {
-        case 0: return pick_extract<16, 16, 16>(kind);
-        case 1: return pick_extract<8, 16, 16>(kind);
-        default: return pick_extract<8, 8, 16>(kind);
-    }
-}
-
-hipError_t init_extract_kernels()
-{
-    for (int cfg = 0; cfg < extract_tile_count(); ++cfg)
-        for (int kind = 0; kind < 3; ++kind) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(extract_entry_point(cfg, kind)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
+VT_BOX_KERNELS(extract, extract_tiled<KIND, T::TD, T::TH, T::TW>)
 
 hipError_t launch_extract(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
                           const AffineParams& p, int64_t grid, int lds_bytes, hipStream_t stream)
 {
     if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(extract_entry_point(cfg, interp_kind(interp)), dim3((unsigned)grid), dim3(256), lds_bytes, stream,
+    hipLaunchKernelGGL(extract_kernels.fn[cfg][interp_kind(interp)], dim3((unsigned)grid), dim3(256), lds_bytes, stream,
                        src, out, zeros16, d_tab, p);
     return hipGetLastError();
 }

@@ -7,7 +7,7 @@
 // (extract_sum_tiled, vt_kernels_extractsum.hip, reduces across the boxes instead):
 //
 //   * One 256-thread workgroup per (matrix, box tile) pair; ids are XCD-contiguous and box-major, the tile is extract_pick_tile's and
-//     the Q32.32 stepping restarts where extract_tiled's does, so every sample is extract_tiled's bit for bit.
+//     the Q32.32 stepping restarts where extract_tiled's does, so every sample is extract_tiled's bit for bit (one text, vt_box_common.h).
 //   * A tile that maps wholly outside the valid interval stages nothing and writes a zero partial; tiles cut by the valid interval or
 //     by the end of the box take the canonical float64 inside test; entries whose box fits no LDS allocation gather from global memory
 //     (direct_sample<KIND>) in the same launch.
@@ -19,23 +19,14 @@
 //     are added in ascending tile index by extract_dot_reduce.  No atomics: out[i] is a fixed expression of its own entry.
 //   * The cross-wave step overlays the first 96 bytes of the staged box once every gather is done: the launch allocates no LDS beyond
 //     extract_tiled's (at least 96 bytes).
-#include "vt_internal.h"
-#include "vt_device.h"
+#include "vt_box_common.h"
 
 #include <algorithm>
 
 namespace vt {
 
-// The three sums' terms for one sample, with every rounding the contract names.  The translation unit is compiled with
-// -ffp-contract=fast, under which hipcc ignores `#pragma clang fp contract(off)`: every product is therefore passed through an empty asm
-// statement, which makes it a value of its own (rounded to float64) that no following addition can absorb into a fused multiply-add.
+// The three sums' terms for one sample, with every rounding the contract names: every product goes through rounded() (vt_box_common.h).
 // mask * b and tmpl * b are exact either way (24 + 24 significant bits); (mask * b) * b is the one product whose rounding shows.
-__device__ __forceinline__ double rounded(double x)
-{
-    asm("" : "+v"(x));
-    return x;
-}
-
 __device__ __forceinline__ void dot_add(double& s0, double& s1, double& s2, float mk, float tp, float v)
 {
     const double b = (double)v;
@@ -47,14 +38,6 @@ __device__ __forceinline__ void dot_add(double& s0, double& s1, double& s2, floa
     s2 = s2 + tb;
 }
 
-// lane 0 of the wave ends up with the sum over its 64 lanes, always by the same tree
-__device__ __forceinline__ double wave_tree_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_down(x, off, 64);
-    return x;
-}
-
 // p.nTd / nTh / nTw = box tiles, p.oD / oH / oW = box shape; part holds [box][tile][3] doubles of this launch.
 template <int KIND /*0 linear, 1 cubic (bspline_weights), 2 cubic (bspline fn)*/, int TD, int TH, int TW>
 __global__ __launch_bounds__(256) void extract_dot_tiled(const float* __restrict__ src, double* __restrict__ part,
@@ -62,13 +45,8 @@ __global__ __launch_bounds__(256) void extract_dot_tiled(const float* __restrict
                                                           const float* __restrict__ tmpl, const float* __restrict__ mask,
                                                           const AffineParams p)
 {
-    constexpr int NPOS = TH * TW;
-    static_assert(256 % TW == 0 && (NPOS >= 256 ? NPOS % 256 == 0 : 256 % NPOS == 0), "tile/thread mapping");
-    constexpr int DG = NPOS >= 256 ? 1 : 256 / NPOS;     // depth groups
-    constexpr int NJ = NPOS >= 256 ? NPOS / 256 : 1;     // in-plane passes
-    constexpr int RP = NPOS >= 256 ? 256 / TW : TH;      // tile rows covered per pass
-    constexpr int DPT = TD / DG;                         // planes per thread
-    static_assert(TD % DG == 0, "tile depth / lane groups");
+    using M = BoxTileMap<TD, TH, TW>;
+    constexpr int NJ = M::NJ, RP = M::RP, DPT = M::DPT;
     constexpr bool CUBIC = KIND != 0;
     constexpr int HALO = CUBIC ? 1 : 0;
     constexpr int UNR = CUBIC ? 1 : 4;                   // samples in flight: two cubic ones cost 250 VGPRs, four over 450
@@ -78,20 +56,14 @@ __global__ __launch_bounds__(256) void extract_dot_tiled(const float* __restrict
     const int t = xcd_contiguous(blockIdx.x, gridDim.x);
     const int tiles = p.nTd * p.nTh * p.nTw;
     const int box = t / tiles;                           // wave-uniform: the entry is read with scalar loads
-    const int u = t - box * tiles;
-    const int tw_i = u % p.nTw;
-    const int u2 = u / p.nTw;
-    const int th_i = u2 % p.nTh;
-    const int td_i = u2 / p.nTh;
-    const int d0 = td_i * TD, h0 = th_i * TH, w0 = tw_i * TW;
+    int d0, h0, w0;
+    M::tile_origin(t - box * tiles, p, d0, h0, w0);
     const ExtractEntry& e = tab[box];
     const int ostride = p.oH * p.oW;                     // the box has fewer than 2^31 voxels (checked on the host): 32-bit voxel offsets
     const bool has_mask = mask != nullptr;               // uniform
 
-    const int pos = DG > 1 ? tid % NPOS : tid;
-    const int kw = pos % TW;
-    const int jh0 = pos / TW;
-    const int i0 = DG > 1 ? (tid / NPOS) * DPT : 0;
+    int kw, jh0, i0;
+    M::thread_origin(tid, kw, jh0, i0);
     const int nd = min(DPT, p.oD - d0 - i0);             // planes this thread owns (<= 0: none)
 
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -107,11 +79,7 @@ __global__ __launch_bounds__(256) void extract_dot_tiled(const float* __restrict
                 const int d = d0 + i0 + i;
                 double s[3];
                 bool inside = true;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    s[r] = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                    inside = inside && (s[r] >= p.vlo[r]) && (s[r] < p.vhi[r]);
-                }
+                VT_CANONICAL_INSIDE(inside, s[r_], e, p, d, h, w);
                 if (inside) {
                     const double fzd = floor(s[0]), fyd = floor(s[1]), fxd = floor(s[2]);
                     const float val = direct_sample<KIND>(src, p, (int)fzd, (int)fyd, (int)fxd, (float)(s[0] - fzd), (float)(s[1] - fyd), (float)(s[2] - fxd));
@@ -120,35 +88,22 @@ __global__ __launch_bounds__(256) void extract_dot_tiled(const float* __restrict
             }
         }
     } else {
-        // ---- tile geometry (wave-uniform, float64), as extract_tiled ----
-        double base[3], lo[3], hi[3];
+        double base[3], lo[3];
         bool any_valid = true, all_valid = true;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            base[r] = fma(e.m[4 * r], (double)d0, fma(e.m[4 * r + 1], (double)h0, fma(e.m[4 * r + 2], (double)w0, e.m[4 * r + 3])));
-            lo[r] = base[r] + e.neg[r];
-            hi[r] = base[r] + e.pos[r];
-            any_valid = any_valid && (hi[r] >= p.vlo[r] - kTileMargin) && (lo[r] < p.vhi[r] + kTileMargin);
-            all_valid = all_valid && (lo[r] >= p.vlo[r] + kTileMargin) && (hi[r] < p.vhi[r] - kTileMargin);
-        }
+        VT_BOX_TILE_GEOMETRY(base, lo, any_valid, all_valid, e, p, d0, h0, w0);
 
         if (any_valid) {                                 // else the whole tile maps outside the valid interval: nothing staged, a zero partial
-            // integer origin of the staged box (finite and small: the tile meets the valid interval, its extent was bounded on the host)
             int o[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;     // (vt_device.h: kBoxMargin)
-            o[2] &= ~3;
+            box_origin<HALO>(lo, o);
 
             const int Lx = e.Lx, Ly = e.Ly, Lz = e.Lz;
             stage_box(lds, src, zeros16, p, o, Lz, Ly, Lx, tid);
             __syncthreads();     // hipcc drains the direct-to-LDS loads (vmcnt(0)) ahead of the barrier
 
             double b[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) b[r] = base[r] - (double)o[r];
+            box_base(base, o, b);
             const int LyLx = Ly * Lx;
-            const int inc_hi0 = e.inc_hi[0], inc_hi1 = e.inc_hi[1], inc_hi2 = e.inc_hi[2];
-            const unsigned inc_lo0 = e.inc_lo[0], inc_lo1 = e.inc_lo[1], inc_lo2 = e.inc_lo[2];
+            const FxInc3 inc = fx_inc3(e);
             const bool whole = all_valid && (p.oD - d0 >= TD);   // wave-uniform
 
 #pragma unroll
@@ -156,38 +111,29 @@ __global__ __launch_bounds__(256) void extract_dot_tiled(const float* __restrict
                 const int j = jh0 + jj * RP;
                 const int h = h0 + j, w = w0 + kw;
                 if (h >= p.oH || w >= p.oW) continue;
-                const double c0d = fma(e.m[0], (double)i0, fma(e.m[1], (double)j, fma(e.m[2], (double)kw, b[0])));
-                const double c1d = fma(e.m[4], (double)i0, fma(e.m[5], (double)j, fma(e.m[6], (double)kw, b[1])));
-                const double c2d = fma(e.m[8], (double)i0, fma(e.m[9], (double)j, fma(e.m[10], (double)kw, b[2])));
-                Fx c0 = to_fx(c0d), c1 = to_fx(c1d), c2 = to_fx(c2d);
+                Fx c0, c1, c2;
+                fx_start3(e, b, i0, j, kw, c0, c1, c2);
                 const int vox = ((d0 + i0) * p.oH + h) * p.oW + w;
                 if (whole) {
 #pragma unroll UNR
                     for (int i = 0; i < DPT; ++i) {
                         const float val = sample_box<KIND>(lds, Lx, LyLx, c0.hi, c1.hi, c2.hi, fx_frac(c0), fx_frac(c1), fx_frac(c2));
                         dot_add(s0, s1, s2, has_mask ? mask[vox + i * ostride] : 1.0f, tmpl[vox + i * ostride], val);
-                        fx_step(c0, inc_hi0, inc_lo0);
-                        fx_step(c1, inc_hi1, inc_lo1);
-                        fx_step(c2, inc_hi2, inc_lo2);
+                        fx_step3(c0, c1, c2, inc);
                     }
                 } else {
-                    // tiles cut by the valid interval or by the end of the box: the inside test is the canonical float64 chain
-                    // (affine_direct's and the oracle's), the taps still come from the fixed-point split
+                    // tiles cut by the valid interval or by the end of the box: the inside test is the canonical chain, the taps still
+                    // come from the fixed-point split
                     for (int i = 0; i < nd; ++i) {
                         float val = sample_box<KIND>(lds, Lx, LyLx, c0.hi, c1.hi, c2.hi, fx_frac(c0), fx_frac(c1), fx_frac(c2));
                         int d = d0 + i0 + i;
                         // the float64 chain starts once the sample is complete: scheduled among the cubic taps it costs 40 VGPRs
                         asm volatile("" : "+v"(d), "+v"(val));
+                        double s;
                         bool inside = true;
-#pragma unroll
-                        for (int r = 0; r < 3; ++r) {
-                            const double s = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                            inside = inside && (s >= p.vlo[r]) && (s < p.vhi[r]);
-                        }
+                        VT_CANONICAL_INSIDE(inside, s, e, p, d, h, w);
                         if (inside) dot_add(s0, s1, s2, has_mask ? mask[vox + i * ostride] : 1.0f, tmpl[vox + i * ostride], val);
-                        fx_step(c0, inc_hi0, inc_lo0);
-                        fx_step(c1, inc_hi1, inc_lo1);
-                        fx_step(c2, inc_hi2, inc_lo2);
+                        fx_step3(c0, c1, c2, inc);
                     }
                 }
             }
@@ -225,37 +171,7 @@ __global__ __launch_bounds__(256) void extract_dot_reduce(const double* __restri
 // host side
 // ---------------------------------------------------------------------------------------------------
 
-typedef void (*extract_dot_fn)(const float*, double*, const float*, const ExtractEntry*, const float*, const float*, const AffineParams);
-
-template <int TD, int TH, int TW>
-static extract_dot_fn pick_extract_dot(int kind)
-{
-    switch (kind) {
-        case 0: return extract_dot_tiled<0, TD, TH, TW>;
-        case 1: return extract_dot_tiled<1, TD, TH, TW>;
-        default: return extract_dot_tiled<2, TD, TH, TW>;
-    }
-}
-
-static extract_dot_fn extract_dot_entry_point(int cfg, int kind)      // the extraction kernel's tile table (extract_tile)
-{
-    switch (cfg) {
-        case 0: return pick_extract_dot<16, 16, 16>(kind);
-        case 1: return pick_extract_dot<8, 16, 16>(kind);
-        default: return pick_extract_dot<8, 8, 16>(kind);
-    }
-}
-
-hipError_t init_extractdot_kernels()
-{
-    for (int cfg = 0; cfg < extract_tile_count(); ++cfg)
-        for (int kind = 0; kind < 3; ++kind) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(extract_dot_entry_point(cfg, kind)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
+VT_BOX_KERNELS(extractdot, extract_dot_tiled<KIND, T::TD, T::TH, T::TW>)
 
 int extract_dot_min_lds() { return 4 * 3 * (int)sizeof(double); }
 
@@ -268,7 +184,7 @@ hipError_t launch_extract_dot(int cfg, int interp, const float* src, double* out
     const int64_t grid = tiles * cnt;
     if (cnt <= 0 || tiles <= 0 || grid > 0x7fffffffLL || !part || !out || !d_tmpl || lds_bytes < extract_dot_min_lds() || lds_bytes > 160 * 1024)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(extract_dot_entry_point(cfg, interp_kind(interp)), dim3((unsigned)grid), dim3(256), lds_bytes, stream,
+    hipLaunchKernelGGL(extractdot_kernels.fn[cfg][interp_kind(interp)], dim3((unsigned)grid), dim3(256), lds_bytes, stream,
                        src, part, zeros16, d_tab, d_tmpl, d_mask, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

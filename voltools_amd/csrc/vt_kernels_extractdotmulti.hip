@@ -7,7 +7,8 @@
 // kind 14) writes into its columns 0, 1, 2 for template j; the difference is that each (matrix, box tile) is staged once and each
 // (matrix, voxel) sampled once, whatever k is:
 //
-//   * One 256-thread workgroup per (matrix, box tile) pair, ids, entries, tile, staging, stepping and inside tests as extract_dot_tiled.
+//   * One 256-thread workgroup per (matrix, box tile) pair, ids, entries, tile, staging, stepping and inside tests as extract_dot_tiled
+//     (vt_box_common.h holds them once, with rounded() and wave_tree_sum()).
 //   * Sampling phase: a thread owns NJ x DPT voxels (4, 8 or 16) and keeps their samples in registers (every loop over them is fully
 //     unrolled).  A voxel that maps outside, or lies beyond the end of the box, is held as +0.
 //   * Scoring phase, without the LDS box: columns are served three at a time (S0, S1 and template 0 first, then templates 1..3, 4..6,
@@ -19,29 +20,11 @@
 //   * The cross-wave step overlays the first 96 bytes of the staged box once every gather is done, three columns per pass: the launch
 //     allocates no LDS beyond extract_tiled's (at least 96 bytes), and the entries are routed exactly as extract_tiled routes them.
 //   * extract_dot_multi_reduce adds the tiles of a box in ascending tile index, one thread per output number.  No atomics.
-#include "vt_internal.h"
-#include "vt_device.h"
+#include "vt_box_common.h"
 
 #include <algorithm>
 
 namespace vt {
-
-// rounded(), the term order and the tree are extract_dot_tiled's (vt_kernels_extractdot.hip), repeated here so that kernel 14's translation
-// unit stays as it is.  The file is compiled with -ffp-contract=fast: a product passed through the empty asm statement is a value of its
-// own that no following addition can absorb into a fused multiply-add.
-__device__ __forceinline__ double rounded_product(double x)
-{
-    asm("" : "+v"(x));
-    return x;
-}
-
-// lane 0 of the wave ends up with the sum over its 64 lanes, always by the same tree
-__device__ __forceinline__ double wave_tree_sum64(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_down(x, off, 64);
-    return x;
-}
 
 // Sixteen held samples times three columns are 48 template loads with 48 64-bit addresses: 226 VGPRs.  The offsets of the second eight
 // voxels are made to wait for the sums over the first eight, so that only 24 loads and their addresses are live at a time.
@@ -60,14 +43,8 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
                                                                 const float* __restrict__ tmpls, const float* __restrict__ mask,
                                                                 const int k, const AffineParams p)
 {
-    constexpr int NPOS = TH * TW;
-    static_assert(256 % TW == 0 && (NPOS >= 256 ? NPOS % 256 == 0 : 256 % NPOS == 0), "tile/thread mapping");
-    constexpr int DG = NPOS >= 256 ? 1 : 256 / NPOS;     // depth groups
-    constexpr int NJ = NPOS >= 256 ? NPOS / 256 : 1;     // in-plane passes
-    constexpr int RP = NPOS >= 256 ? 256 / TW : TH;      // tile rows covered per pass
-    constexpr int DPT = TD / DG;                         // planes per thread
-    static_assert(TD % DG == 0, "tile depth / lane groups");
-    constexpr int NV = NJ * DPT;                         // voxels (held samples) per thread
+    using M = BoxTileMap<TD, TH, TW>;
+    constexpr int NJ = M::NJ, RP = M::RP, DPT = M::DPT, NV = M::NV;
     static_assert(NV <= 16, "held samples per thread");
     constexpr int SCORE_CHUNK = 8;                       // voxels whose template loads (three columns each) are in flight together
     constexpr bool CUBIC = KIND != 0;
@@ -78,21 +55,15 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
     const int t = xcd_contiguous(blockIdx.x, gridDim.x);
     const int tiles = p.nTd * p.nTh * p.nTw;
     const int box = t / tiles;                           // wave-uniform: the entry is read with scalar loads
-    const int u = t - box * tiles;
-    const int tw_i = u % p.nTw;
-    const int u2 = u / p.nTw;
-    const int th_i = u2 % p.nTh;
-    const int td_i = u2 / p.nTh;
-    const int d0 = td_i * TD, h0 = th_i * TH, w0 = tw_i * TW;
+    int d0, h0, w0;
+    M::tile_origin(t - box * tiles, p, d0, h0, w0);
     const ExtractEntry& e = tab[box];
     const int ostride = p.oH * p.oW;                     // the box has fewer than 2^31 voxels (checked on the host): 32-bit voxel offsets
     const int ncol = 2 + k;
     double* const my_part = part + (int64_t)t * ncol;
 
-    const int pos = DG > 1 ? tid % NPOS : tid;
-    const int kw = pos % TW;
-    const int jh0 = pos / TW;
-    const int i0 = DG > 1 ? (tid / NPOS) * DPT : 0;
+    int kw, jh0, i0;
+    M::thread_origin(tid, kw, jh0, i0);
     const int nd = min(DPT, p.oD - d0 - i0);             // planes this thread owns (<= 0: none)
 
     float val[NV];                                       // the samples of this thread's voxels, (in-plane pass, plane) order; +0: none
@@ -111,11 +82,7 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
                 const int d = d0 + i0 + i;
                 double s[3];
                 bool inside = true;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    s[r] = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                    inside = inside && (s[r] >= p.vlo[r]) && (s[r] < p.vhi[r]);
-                }
+                VT_CANONICAL_INSIDE(inside, s[r_], e, p, d, h, w);
                 if (inside) {
                     const double fzd = floor(s[0]), fyd = floor(s[1]), fxd = floor(s[2]);
                     val[jj * DPT + i] = direct_sample<KIND>(src, p, (int)fzd, (int)fyd, (int)fxd, (float)(s[0] - fzd), (float)(s[1] - fyd), (float)(s[2] - fxd));
@@ -123,38 +90,25 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
             }
         }
     } else {
-        // ---- tile geometry (wave-uniform, float64), as extract_tiled ----
-        double base[3], lo[3], hi[3];
+        double base[3], lo[3];
         bool any_valid = true, all_valid = true;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            base[r] = fma(e.m[4 * r], (double)d0, fma(e.m[4 * r + 1], (double)h0, fma(e.m[4 * r + 2], (double)w0, e.m[4 * r + 3])));
-            lo[r] = base[r] + e.neg[r];
-            hi[r] = base[r] + e.pos[r];
-            any_valid = any_valid && (hi[r] >= p.vlo[r] - kTileMargin) && (lo[r] < p.vhi[r] + kTileMargin);
-            all_valid = all_valid && (lo[r] >= p.vlo[r] + kTileMargin) && (hi[r] < p.vhi[r] - kTileMargin);
-        }
+        VT_BOX_TILE_GEOMETRY(base, lo, any_valid, all_valid, e, p, d0, h0, w0);
 
         if (!any_valid) {                                // the whole tile maps outside the valid interval: nothing staged, a zero partial
             for (int c = tid; c < ncol; c += 256) my_part[c] = 0.0;      // workgroup-uniform exit, ahead of every barrier
             return;
         }
-        // integer origin of the staged box (finite and small: the tile meets the valid interval, its extent was bounded on the host)
         int o[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;     // (vt_device.h: kBoxMargin)
-        o[2] &= ~3;
+        box_origin<HALO>(lo, o);
 
         const int Lx = e.Lx, Ly = e.Ly, Lz = e.Lz;
         stage_box(lds, src, zeros16, p, o, Lz, Ly, Lx, tid);
         __syncthreads();     // hipcc drains the direct-to-LDS loads (vmcnt(0)) ahead of the barrier
 
         double b[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) b[r] = base[r] - (double)o[r];
+        box_base(base, o, b);
         const int LyLx = Ly * Lx;
-        const int inc_hi0 = e.inc_hi[0], inc_hi1 = e.inc_hi[1], inc_hi2 = e.inc_hi[2];
-        const unsigned inc_lo0 = e.inc_lo[0], inc_lo1 = e.inc_lo[1], inc_lo2 = e.inc_lo[2];
+        const FxInc3 inc = fx_inc3(e);
         const bool whole = all_valid && (p.oD - d0 >= TD);   // wave-uniform
 
 #pragma unroll
@@ -162,10 +116,8 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
             const int j = jh0 + jj * RP;
             const int h = h0 + j, w = w0 + kw;
             if (h >= p.oH || w >= p.oW) continue;
-            const double c0d = fma(e.m[0], (double)i0, fma(e.m[1], (double)j, fma(e.m[2], (double)kw, b[0])));
-            const double c1d = fma(e.m[4], (double)i0, fma(e.m[5], (double)j, fma(e.m[6], (double)kw, b[1])));
-            const double c2d = fma(e.m[8], (double)i0, fma(e.m[9], (double)j, fma(e.m[10], (double)kw, b[2])));
-            Fx c0 = to_fx(c0d), c1 = to_fx(c1d), c2 = to_fx(c2d);
+            Fx c0, c1, c2;
+            fx_start3(e, b, i0, j, kw, c0, c1, c2);
             if (whole) {
 #pragma unroll
                 for (int i = 0; i < DPT; ++i) {
@@ -174,13 +126,11 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
                     // (four trilinear ones, kernel 14's UNR)
                     if (CUBIC || (i & 3) == 3) asm volatile("" : "+v"(s), "+v"(c0.hi), "+v"(c1.hi), "+v"(c2.hi));
                     val[jj * DPT + i] = s;
-                    fx_step(c0, inc_hi0, inc_lo0);
-                    fx_step(c1, inc_hi1, inc_lo1);
-                    fx_step(c2, inc_hi2, inc_lo2);
+                    fx_step3(c0, c1, c2, inc);
                 }
             } else {
-                // tiles cut by the valid interval or by the end of the box: the inside test is the canonical float64 chain
-                // (affine_direct's and the oracle's), the taps still come from the fixed-point split
+                // tiles cut by the valid interval or by the end of the box: the inside test is the canonical chain, the taps still come
+                // from the fixed-point split
 #pragma unroll
                 for (int i = 0; i < DPT; ++i) {
                     if (i >= nd) continue;
@@ -188,16 +138,11 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
                     int d = d0 + i0 + i;
                     // the float64 chain starts once the sample is complete, and so do the next plane's taps
                     asm volatile("" : "+v"(d), "+v"(s), "+v"(c0.hi), "+v"(c1.hi), "+v"(c2.hi));
+                    double sd;
                     bool inside = true;
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        const double sr = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                        inside = inside && (sr >= p.vlo[r]) && (sr < p.vhi[r]);
-                    }
+                    VT_CANONICAL_INSIDE(inside, sd, e, p, d, h, w);
                     val[jj * DPT + i] = inside ? s : 0.0f;
-                    fx_step(c0, inc_hi0, inc_lo0);
-                    fx_step(c1, inc_hi1, inc_lo1);
-                    fx_step(c2, inc_hi2, inc_lo2);
+                    fx_step3(c0, c1, c2, inc);
                 }
             }
         }
@@ -228,9 +173,9 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
                 const float mk = has_mask ? mask[off[q]] : 1.0f;
                 const float tp = tmpls[off[q]];
                 const double bq = (double)val[q];
-                const double mb = rounded_product((double)mk * bq);      // exact
-                const double tb = rounded_product((double)tp * bq);      // exact
-                const double mbb = rounded_product(mb * bq);             // rounded once
+                const double mb = rounded((double)mk * bq);      // exact
+                const double tb = rounded((double)tp * bq);      // exact
+                const double mbb = rounded(mb * bq);             // rounded once
                 a0 = a0 + mb;
                 a1 = a1 + mbb;
                 a2 = a2 + tb;
@@ -243,15 +188,15 @@ __global__ __launch_bounds__(256) void extract_dot_multi_tiled(const float* __re
             for (int q = 0; q < NV; ++q) {
                 if (q == SCORE_CHUNK) score_fence(a0, a1, a2, off);
                 const double bq = (double)val[q];
-                a0 = a0 + rounded_product((double)t0[off[q]] * bq);
-                a1 = a1 + rounded_product((double)t1[off[q]] * bq);
-                a2 = a2 + rounded_product((double)t2[off[q]] * bq);
+                a0 = a0 + rounded((double)t0[off[q]] * bq);
+                a1 = a1 + rounded((double)t1[off[q]] * bq);
+                a2 = a2 + rounded((double)t2[off[q]] * bq);
             }
         }
         // 256 partial triples -> one, by extract_dot_tiled's tree
-        a0 = wave_tree_sum64(a0);
-        a1 = wave_tree_sum64(a1);
-        a2 = wave_tree_sum64(a2);
+        a0 = wave_tree_sum(a0);
+        a1 = wave_tree_sum(a1);
+        a2 = wave_tree_sum(a2);
         __syncthreads();         // first pass: every gather of the staged box is done, its first 96 bytes become the cross-wave scratch;
                                  // later passes: the previous pass has read the scratch
         if ((tid & 63) == 0) { red[3 * wv] = a0; red[3 * wv + 1] = a1; red[3 * wv + 2] = a2; }
@@ -278,38 +223,7 @@ __global__ __launch_bounds__(256) void extract_dot_multi_reduce(const double* __
 // host side
 // ---------------------------------------------------------------------------------------------------
 
-typedef void (*extract_dot_multi_fn)(const float*, double*, const float*, const ExtractEntry*, const float*, const float*, const int,
-                                     const AffineParams);
-
-template <int TD, int TH, int TW>
-static extract_dot_multi_fn pick_extract_dot_multi(int kind)
-{
-    switch (kind) {
-        case 0: return extract_dot_multi_tiled<0, TD, TH, TW>;
-        case 1: return extract_dot_multi_tiled<1, TD, TH, TW>;
-        default: return extract_dot_multi_tiled<2, TD, TH, TW>;
-    }
-}
-
-static extract_dot_multi_fn extract_dot_multi_entry_point(int cfg, int kind)      // the extraction kernel's tile table (extract_tile)
-{
-    switch (cfg) {
-        case 0: return pick_extract_dot_multi<16, 16, 16>(kind);
-        case 1: return pick_extract_dot_multi<8, 16, 16>(kind);
-        default: return pick_extract_dot_multi<8, 8, 16>(kind);
-    }
-}
-
-hipError_t init_extractdotmulti_kernels()
-{
-    for (int cfg = 0; cfg < extract_tile_count(); ++cfg)
-        for (int kind = 0; kind < 3; ++kind) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(extract_dot_multi_entry_point(cfg, kind)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
+VT_BOX_KERNELS(extractdotmulti, extract_dot_multi_tiled<KIND, T::TD, T::TH, T::TW>)
 
 // grid = box tiles x cnt workgroups, then one thread per output number; `part` holds cnt x tiles x (2 + k) doubles, `out` cnt x (2 + k).
 hipError_t launch_extract_dot_multi(int cfg, int interp, const float* src, double* out, double* part, const float* zeros16,
@@ -321,7 +235,7 @@ hipError_t launch_extract_dot_multi(int cfg, int interp, const float* src, doubl
     if (cnt <= 0 || k <= 0 || k > 0x7fffffff - 2 || tiles <= 0 || grid > 0x7fffffffLL || !part || !out || !d_tmpls ||
         lds_bytes < extract_dot_min_lds() || lds_bytes > 160 * 1024)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(extract_dot_multi_entry_point(cfg, interp_kind(interp)), dim3((unsigned)grid), dim3(256), lds_bytes, stream,
+    hipLaunchKernelGGL(extractdotmulti_kernels.fn[cfg][interp_kind(interp)], dim3((unsigned)grid), dim3(256), lds_bytes, stream,
                        src, part, zeros16, d_tab, d_tmpls, d_mask, k, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -7,11 +7,11 @@
 //
 //   * One 256-thread workgroup per (segment of consecutive matrices, box tile); ids are XCD-contiguous and segment-major, so
 //     the tiles of one segment are neighbours on one XCD and walk the same matrices at about the same time.
-//   * The thread mapping is extract_tiled's: a thread owns NJ * DPT output voxels of its tile and keeps one float64
+//   * The thread mapping is the box family's (vt_box_common.h: BoxTileMap): a thread owns NJ * DPT output voxels of its tile and keeps one float64
 //     accumulator for each (16 / 8 / 4 for the 16^3 / 8x16x16 / 8x8x16 tiles).  No two lanes share a voxel: no atomics, no
 //     exchange through LDS.
 //   * Per matrix, in ascending order: ExtractEntry and weight by scalar loads, float64 tile bounding box; a tile that clears
-//     the valid interval adds nothing and stages nothing; otherwise stage_box, barrier, sample_box<KIND> with extract_tiled's
+//     the valid interval adds nothing and stages nothing; otherwise stage_box, barrier, sample_box<KIND> with the family's
 //     Q32.32 stepping (same restart points, hence the same float32 samples), barrier.  Tiles cut by the valid interval or by
 //     the end of the box take the canonical float64 inside test.  Entries whose box fits no LDS allocation gather from global
 //     memory (direct_sample<KIND>) inside the same loop.
@@ -19,20 +19,11 @@
 //     fused multiply-add: the expression is the one a host loop in float64 evaluates).  A launch with one segment rounds to
 //     float32 and stores; otherwise the workgroup stores float64 partials [segment][d][h][w] and project_reduce adds the
 //     segments in ascending order and rounds once.
-#include "vt_internal.h"
-#include "vt_device.h"
+#include "vt_box_common.h"
 
 #include <algorithm>
 
 namespace vt {
-
-// acc + w * v in float64 with both roundings (the translation unit is compiled with -ffp-contract=fast)
-__device__ __forceinline__ double weighted_add(double acc, double w, float v)
-{
-#pragma clang fp contract(off)
-    const double t = w * (double)v;
-    return acc + t;
-}
 
 // p.nTd / nTh / nTw = box tiles, p.oD / oH / oW = box shape; n matrices in segments of per_seg consecutive ones.
 template <int KIND /*0 linear, 1 cubic (bspline_weights), 2 cubic (bspline fn)*/, int TD, int TH, int TW>
@@ -41,13 +32,8 @@ __global__ __launch_bounds__(256) void extract_sum_tiled(const float* __restrict
                                                           const double* __restrict__ wts, const int n, const int per_seg,
                                                           const AffineParams p)
 {
-    constexpr int NPOS = TH * TW;
-    static_assert(256 % TW == 0 && (NPOS >= 256 ? NPOS % 256 == 0 : 256 % NPOS == 0), "tile/thread mapping");
-    constexpr int DG = NPOS >= 256 ? 1 : 256 / NPOS;     // depth groups
-    constexpr int NJ = NPOS >= 256 ? NPOS / 256 : 1;     // in-plane passes
-    constexpr int RP = NPOS >= 256 ? 256 / TW : TH;      // tile rows covered per pass
-    constexpr int DPT = TD / DG;                         // planes per thread
-    static_assert(TD % DG == 0, "tile depth / lane groups");
+    using M = BoxTileMap<TD, TH, TW>;
+    constexpr int NJ = M::NJ, RP = M::RP, DPT = M::DPT;
     constexpr bool CUBIC = KIND != 0;
     constexpr int HALO = CUBIC ? 1 : 0;
     constexpr int UNR = CUBIC ? 2 : 4;                   // samples in flight (project_tiled's: four cubic ones take one wave per SIMD)
@@ -57,18 +43,12 @@ __global__ __launch_bounds__(256) void extract_sum_tiled(const float* __restrict
     const int t = xcd_contiguous(blockIdx.x, gridDim.x);
     const int tiles = p.nTd * p.nTh * p.nTw;
     const int seg = t / tiles;                           // segment-major
-    const int u = t - seg * tiles;
-    const int tw_i = u % p.nTw;
-    const int u2 = u / p.nTw;
-    const int th_i = u2 % p.nTh;
-    const int td_i = u2 / p.nTh;
-    const int d0 = td_i * TD, h0 = th_i * TH, w0 = tw_i * TW;
+    int d0, h0, w0;
+    M::tile_origin(t - seg * tiles, p, d0, h0, w0);
     const int64_t ostride = (int64_t)p.oH * p.oW;
 
-    const int pos = DG > 1 ? tid % NPOS : tid;
-    const int kw = pos % TW;
-    const int jh0 = pos / TW;
-    const int i0 = DG > 1 ? (tid / NPOS) * DPT : 0;
+    int kw, jh0, i0;
+    M::thread_origin(tid, kw, jh0, i0);
     const int nd = min(DPT, p.oD - d0 - i0);             // planes this thread owns (<= 0: none)
 
     double acc[NJ * DPT];                                // statically indexed throughout: registers
@@ -96,11 +76,7 @@ __global__ __launch_bounds__(256) void extract_sum_tiled(const float* __restrict
                         const int d = d0 + i0 + i;
                         double s[3];
                         bool inside = true;
-#pragma unroll
-                        for (int r = 0; r < 3; ++r) {
-                            s[r] = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                            inside = inside && (s[r] >= p.vlo[r]) && (s[r] < p.vhi[r]);
-                        }
+                        VT_CANONICAL_INSIDE(inside, s[r_], e, p, d, h, w);
                         if (inside) {
                             const double fzd = floor(s[0]), fyd = floor(s[1]), fxd = floor(s[2]);
                             a = weighted_add(a, wt, direct_sample<KIND>(src, p, (int)fzd, (int)fyd, (int)fxd, (float)(s[0] - fzd),
@@ -115,35 +91,22 @@ __global__ __launch_bounds__(256) void extract_sum_tiled(const float* __restrict
             continue;
         }
 
-        // ---- tile geometry (wave-uniform, float64), as extract_tiled ----
-        double base[3], lo[3], hi[3];
+        double base[3], lo[3];
         bool any_valid = true, all_valid = true;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            base[r] = fma(e.m[4 * r], (double)d0, fma(e.m[4 * r + 1], (double)h0, fma(e.m[4 * r + 2], (double)w0, e.m[4 * r + 3])));
-            lo[r] = base[r] + e.neg[r];
-            hi[r] = base[r] + e.pos[r];
-            any_valid = any_valid && (hi[r] >= p.vlo[r] - kTileMargin) && (lo[r] < p.vhi[r] + kTileMargin);
-            all_valid = all_valid && (lo[r] >= p.vlo[r] + kTileMargin) && (hi[r] < p.vhi[r] - kTileMargin);
-        }
+        VT_BOX_TILE_GEOMETRY(base, lo, any_valid, all_valid, e, p, d0, h0, w0);
         if (!any_valid) continue;                        // the whole tile maps outside the valid interval: nothing staged, nothing added
 
-        // integer origin of the staged box (finite and small: the tile meets the valid interval, its extent was bounded on the host)
         int o[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;     // (vt_device.h: kBoxMargin)
-        o[2] &= ~3;
+        box_origin<HALO>(lo, o);
 
         const int Lx = e.Lx, Ly = e.Ly, Lz = e.Lz;
         stage_box(lds, src, zeros16, p, o, Lz, Ly, Lx, tid);
         __syncthreads();     // hipcc drains the direct-to-LDS loads (vmcnt(0)) ahead of the barrier
 
         double b[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) b[r] = base[r] - (double)o[r];
+        box_base(base, o, b);
         const int LyLx = Ly * Lx;
-        const int inc_hi0 = e.inc_hi[0], inc_hi1 = e.inc_hi[1], inc_hi2 = e.inc_hi[2];
-        const unsigned inc_lo0 = e.inc_lo[0], inc_lo1 = e.inc_lo[1], inc_lo2 = e.inc_lo[2];
+        const FxInc3 inc = fx_inc3(e);
         const bool whole = all_valid && (p.oD - d0 >= TD);   // wave-uniform
 
 #pragma unroll
@@ -151,10 +114,8 @@ __global__ __launch_bounds__(256) void extract_sum_tiled(const float* __restrict
             const int j = jh0 + jj * RP;
             const int h = h0 + j, w = w0 + kw;
             if (h >= p.oH || w >= p.oW) continue;
-            const double s0 = fma(e.m[0], (double)i0, fma(e.m[1], (double)j, fma(e.m[2], (double)kw, b[0])));
-            const double s1 = fma(e.m[4], (double)i0, fma(e.m[5], (double)j, fma(e.m[6], (double)kw, b[1])));
-            const double s2 = fma(e.m[8], (double)i0, fma(e.m[9], (double)j, fma(e.m[10], (double)kw, b[2])));
-            Fx c0 = to_fx(s0), c1 = to_fx(s1), c2 = to_fx(s2);
+            Fx c0, c1, c2;
+            fx_start3(e, b, i0, j, kw, c0, c1, c2);
             // Every plane of the tile is sampled (the staged box covers the whole tile, as in extract_tiled, where cut tiles sample
             // before they mask); planes beyond the box and voxels that fail the inside test are not added.  UNR samples per trip; the
             // accumulators rotate by UNR per trip so that they are indexed statically (registers), DPT / UNR trips = identity.
@@ -166,21 +127,16 @@ __global__ __launch_bounds__(256) void extract_sum_tiled(const float* __restrict
                 for (int k = 0; k < UNR; ++k) {
                     bool inside = true;
                     if (!whole) {
-                        // tiles cut by the valid interval or by the end of the box: the inside test is the canonical float64 chain
-                        // (affine_direct's and the oracle's), the taps still come from the fixed-point split
+                        // tiles cut by the valid interval or by the end of the box: the inside test is the canonical chain, the taps
+                        // still come from the fixed-point split
                         const int d = d0 + i0 + ib + k;
+                        double s;
                         inside = ib + k < nd;
-#pragma unroll
-                        for (int r = 0; r < 3; ++r) {
-                            const double s = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                            inside = inside && (s >= p.vlo[r]) && (s < p.vhi[r]);
-                        }
+                        VT_CANONICAL_INSIDE(inside, s, e, p, d, h, w);
                     }
                     const float val = sample_box<KIND>(lds, Lx, LyLx, c0.hi, c1.hi, c2.hi, fx_frac(c0), fx_frac(c1), fx_frac(c2));
                     a[k] = inside ? weighted_add(acc[jj * DPT + k], wt, val) : acc[jj * DPT + k];
-                    fx_step(c0, inc_hi0, inc_lo0);
-                    fx_step(c1, inc_hi1, inc_lo1);
-                    fx_step(c2, inc_hi2, inc_lo2);
+                    fx_step3(c0, c1, c2, inc);
                 }
 #pragma unroll
                 for (int k = 0; k + UNR < DPT; ++k) acc[jj * DPT + k] = acc[jj * DPT + k + UNR];
@@ -230,37 +186,7 @@ void extract_sum_shape_plan(bool cubic, const int box[3], int n, int* cfg, int* 
     *nseg = (int)((n + *per_seg - 1) / *per_seg);
 }
 
-typedef void (*extract_sum_fn)(const float*, float*, double*, const float*, const ExtractEntry*, const double*, int, int, const AffineParams);
-
-template <int TD, int TH, int TW>
-static extract_sum_fn pick_extract_sum(int kind)
-{
-    switch (kind) {
-        case 0: return extract_sum_tiled<0, TD, TH, TW>;
-        case 1: return extract_sum_tiled<1, TD, TH, TW>;
-        default: return extract_sum_tiled<2, TD, TH, TW>;
-    }
-}
-
-static extract_sum_fn extract_sum_entry_point(int cfg, int kind)      // the extraction kernel's tile table (extract_tile)
-{
-    switch (cfg) {
-        case 0: return pick_extract_sum<16, 16, 16>(kind);
-        case 1: return pick_extract_sum<8, 16, 16>(kind);
-        default: return pick_extract_sum<8, 8, 16>(kind);
-    }
-}
-
-hipError_t init_extractsum_kernels()
-{
-    for (int cfg = 0; cfg < extract_tile_count(); ++cfg)
-        for (int kind = 0; kind < 3; ++kind) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(extract_sum_entry_point(cfg, kind)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
+VT_BOX_KERNELS(extractsum, extract_sum_tiled<KIND, T::TD, T::TH, T::TW>)
 
 // grid = box tiles x nseg workgroups; with nseg > 1 `part` holds nseg x box voxels doubles and the caller follows with
 // launch_project_reduce(part, out, nseg, box voxels, 1, stream).
@@ -271,7 +197,7 @@ hipError_t launch_extract_sum(int cfg, int interp, const float* src, float* out,
     const int64_t grid = (int64_t)p.nTd * p.nTh * p.nTw * nseg;
     if (grid <= 0 || grid > 0x7fffffffLL || n <= 0 || per_seg <= 0 || (int64_t)per_seg * nseg < n || (nseg > 1 && !part))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(extract_sum_entry_point(cfg, interp_kind(interp)), dim3((unsigned)grid), dim3(256), lds_bytes, stream,
+    hipLaunchKernelGGL(extractsum_kernels.fn[cfg][interp_kind(interp)], dim3((unsigned)grid), dim3(256), lds_bytes, stream,
                        src, out, part, zeros16, d_tab, d_wts, n, per_seg, p);
     return hipGetLastError();
 }

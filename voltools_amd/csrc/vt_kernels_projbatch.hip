@@ -6,7 +6,7 @@
 //
 //   * One 256-thread workgroup per (matrix, h-tile, w-tile, depth segment); ids are XCD-contiguous and matrix-major.  The
 //     workgroup reads its matrix's ExtractEntry with scalar loads and marches over the TD-deep tiles of its segment.
-//   * Per tile: float64 bounding box (extract_tiled's), skipped outright when it clears the valid interval; otherwise
+//   * Per tile: float64 bounding box (vt_box_common.h, as every kernel of the box family), skipped outright when it clears the valid interval; otherwise
 //     stage_box, barrier, sample_box<KIND> with the Q32.32 stepping, barrier.  Tiles cut by the valid interval or by the
 //     end of the depth range take the canonical float64 inside test.
 //   * Every sample goes into a per-thread float64 accumulator in depth order; lane groups that split a tile's depth
@@ -16,8 +16,7 @@
 //     output shape, interpolation).
 //   * Entries whose box fits no LDS allocation (strong minification) gather from global memory inside the same launch
 //     (direct_sample<KIND>), with the same accumulation.
-#include "vt_internal.h"
-#include "vt_device.h"
+#include "vt_box_common.h"
 
 #include <algorithm>
 
@@ -29,13 +28,8 @@ __global__ __launch_bounds__(256) void project_tiled(const float* __restrict__ s
                                                       const float* __restrict__ zeros16,
                                                       const ExtractEntry* __restrict__ tab, const AffineParams p)
 {
-    constexpr int NPOS = TH * TW;
-    static_assert(256 % TW == 0 && (NPOS >= 256 ? NPOS % 256 == 0 : 256 % NPOS == 0), "tile/thread mapping");
-    constexpr int DG = NPOS >= 256 ? 1 : 256 / NPOS;     // depth groups
-    constexpr int NJ = NPOS >= 256 ? NPOS / 256 : 1;     // in-plane passes
-    constexpr int RP = NPOS >= 256 ? 256 / TW : TH;      // tile rows covered per pass
-    constexpr int DPT = TD / DG;                         // planes per thread and tile
-    static_assert(TD % DG == 0, "tile depth / lane groups");
+    using M = BoxTileMap<TD, TH, TW>;
+    constexpr int NPOS = M::NPOS, DG = M::DG, NJ = M::NJ, RP = M::RP, DPT = M::DPT;
     constexpr bool CUBIC = KIND != 0;
     constexpr int HALO = CUBIC ? 1 : 0;
     constexpr int UNR = CUBIC ? 2 : 4;                   // samples in flight: four cubic ones take 400 registers (one wave per SIMD), two take 210
@@ -47,18 +41,14 @@ __global__ __launch_bounds__(256) void project_tiled(const float* __restrict__ s
     const int units = nseg * p.nTh * p.nTw;
     const int img = t / units;                           // wave-uniform: the entry is read with scalar loads
     const int u = t - img * units;
-    const int tw_i = u % p.nTw;
-    const int u2 = u / p.nTw;
-    const int th_i = u2 % p.nTh;
-    const int seg = u2 / p.nTh;
-    const int h0 = th_i * TH, w0 = tw_i * TW;
+    int dseg, h0, w0;                                    // the slowest tile index counts depth segments here: dseg = seg * TD
+    M::tile_origin(u, p, dseg, h0, w0);
+    const int seg = dseg / TD;
     const ExtractEntry& e = tab[img];
 
-    const int pos = DG > 1 ? tid % NPOS : tid;
-    const int kw = pos % TW;
-    const int jh0 = pos / TW;
+    int kw, jh0, i0;
+    const int pos = M::thread_origin(tid, kw, jh0, i0);
     const int grp = DG > 1 ? tid / NPOS : 0;
-    const int i0 = grp * DPT;
 
     const int tile_first = seg * p.dch;
     const int tile_end = min(tile_first + p.dch, (p.oD + TD - 1) / TD);
@@ -69,8 +59,7 @@ __global__ __launch_bounds__(256) void project_tiled(const float* __restrict__ s
 
     const int Lx = e.Lx, Ly = e.Ly, Lz = e.Lz;
     const int LyLx = Ly * Lx;
-    const int inc_hi0 = e.inc_hi[0], inc_hi1 = e.inc_hi[1], inc_hi2 = e.inc_hi[2];
-    const unsigned inc_lo0 = e.inc_lo[0], inc_lo1 = e.inc_lo[1], inc_lo2 = e.inc_lo[2];
+    const FxInc3 inc = fx_inc3(e);
 
     if (!e.tiled) {
         // footprint beyond the LDS cap: taps from global memory, coordinates by the canonical chain (affine_direct)
@@ -86,11 +75,7 @@ __global__ __launch_bounds__(256) void project_tiled(const float* __restrict__ s
                     const int d = d0 + i0 + i;
                     double s[3];
                     bool inside = true;
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        s[r] = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                        inside = inside && (s[r] >= p.vlo[r]) && (s[r] < p.vhi[r]);
-                    }
+                    VT_CANONICAL_INSIDE(inside, s[r_], e, p, d, h, w);
                     if (inside) {
                         const double fzd = floor(s[0]), fyd = floor(s[1]), fxd = floor(s[2]);
                         acc[jj] += (double)direct_sample<KIND>(src, p, (int)fzd, (int)fyd, (int)fxd, (float)(s[0] - fzd), (float)(s[1] - fyd),
@@ -104,31 +89,19 @@ __global__ __launch_bounds__(256) void project_tiled(const float* __restrict__ s
             const int d0 = td_i * TD;
             const int nd = min(DPT, p.oD - d0 - i0);         // planes of this tile the thread owns (<= 0: none)
 
-            // ---- tile geometry (wave-uniform, float64), as extract_tiled ----
-            double base[3], lo[3], hi[3];
+            double base[3], lo[3];
             bool any_valid = true, all_valid = true;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                base[r] = fma(e.m[4 * r], (double)d0, fma(e.m[4 * r + 1], (double)h0, fma(e.m[4 * r + 2], (double)w0, e.m[4 * r + 3])));
-                lo[r] = base[r] + e.neg[r];
-                hi[r] = base[r] + e.pos[r];
-                any_valid = any_valid && (hi[r] >= p.vlo[r] - kTileMargin) && (lo[r] < p.vhi[r] + kTileMargin);
-                all_valid = all_valid && (lo[r] >= p.vlo[r] + kTileMargin) && (hi[r] < p.vhi[r] - kTileMargin);
-            }
+            VT_BOX_TILE_GEOMETRY(base, lo, any_valid, all_valid, e, p, d0, h0, w0);
             if (!any_valid) continue;                        // the whole tile maps outside the valid interval: nothing staged, nothing added
 
-            // integer origin of the staged box (finite and small: the tile meets the valid interval, its extent was bounded on the host)
             int o[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;     // (vt_device.h: kBoxMargin)
-            o[2] &= ~3;
+            box_origin<HALO>(lo, o);
 
             stage_box(lds, src, zeros16, p, o, Lz, Ly, Lx, tid);
             __syncthreads();     // hipcc drains the direct-to-LDS loads (vmcnt(0)) ahead of the barrier
 
             double b[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) b[r] = base[r] - (double)o[r];
+            box_base(base, o, b);
             const bool whole = all_valid && (p.oD - d0 >= TD);   // wave-uniform
 
 #pragma unroll
@@ -136,35 +109,26 @@ __global__ __launch_bounds__(256) void project_tiled(const float* __restrict__ s
                 const int j = jh0 + jj * RP;
                 const int h = h0 + j, w = w0 + kw;
                 if (h >= p.oH || w >= p.oW) continue;
-                const double s0 = fma(e.m[0], (double)i0, fma(e.m[1], (double)j, fma(e.m[2], (double)kw, b[0])));
-                const double s1 = fma(e.m[4], (double)i0, fma(e.m[5], (double)j, fma(e.m[6], (double)kw, b[1])));
-                const double s2 = fma(e.m[8], (double)i0, fma(e.m[9], (double)j, fma(e.m[10], (double)kw, b[2])));
-                Fx c0 = to_fx(s0), c1 = to_fx(s1), c2 = to_fx(s2);
+                Fx c0, c1, c2;
+                fx_start3(e, b, i0, j, kw, c0, c1, c2);
                 double a = acc[jj];
                 if (whole) {
 #pragma unroll UNR
                     for (int i = 0; i < DPT; ++i) {
                         a += (double)sample_box<KIND>(lds, Lx, LyLx, c0.hi, c1.hi, c2.hi, fx_frac(c0), fx_frac(c1), fx_frac(c2));
-                        fx_step(c0, inc_hi0, inc_lo0);
-                        fx_step(c1, inc_hi1, inc_lo1);
-                        fx_step(c2, inc_hi2, inc_lo2);
+                        fx_step3(c0, c1, c2, inc);
                     }
                 } else {
-                    // tiles cut by the valid interval or by the end of the depth range: the inside test is the canonical float64 chain
-                    // (affine_direct's and the oracle's), the taps still come from the fixed-point split
+                    // tiles cut by the valid interval or by the end of the depth range: the inside test is the canonical chain, the taps
+                    // still come from the fixed-point split
                     for (int i = 0; i < nd; ++i) {
                         const int d = d0 + i0 + i;
+                        double s;
                         bool inside = true;
-#pragma unroll
-                        for (int r = 0; r < 3; ++r) {
-                            const double s = fma(e.m[4 * r], (double)d, fma(e.m[4 * r + 1], (double)h, fma(e.m[4 * r + 2], (double)w, e.m[4 * r + 3])));
-                            inside = inside && (s >= p.vlo[r]) && (s < p.vhi[r]);
-                        }
+                        VT_CANONICAL_INSIDE(inside, s, e, p, d, h, w);
                         const float val = sample_box<KIND>(lds, Lx, LyLx, c0.hi, c1.hi, c2.hi, fx_frac(c0), fx_frac(c1), fx_frac(c2));
                         a += inside ? (double)val : 0.0;
-                        fx_step(c0, inc_hi0, inc_lo0);
-                        fx_step(c1, inc_hi1, inc_lo1);
-                        fx_step(c2, inc_hi2, inc_lo2);
+                        fx_step3(c0, c1, c2, inc);
                     }
                 }
                 acc[jj] = a;
@@ -233,43 +197,13 @@ void project_batch_shape_plan(bool cubic, int depth, int height, int width, int*
     *nseg = (int)((ntd + *tiles_per_seg - 1) / *tiles_per_seg);
 }
 
-typedef void (*project_fn)(const float*, float*, double*, const float*, const ExtractEntry*, const AffineParams);
-
-template <int TD, int TH, int TW>
-static project_fn pick_project(int kind)
-{
-    switch (kind) {
-        case 0: return project_tiled<0, TD, TH, TW>;
-        case 1: return project_tiled<1, TD, TH, TW>;
-        default: return project_tiled<2, TD, TH, TW>;
-    }
-}
-
-static project_fn project_entry_point(int cfg, int kind)      // the extraction kernel's tile table (extract_tile)
-{
-    switch (cfg) {
-        case 0: return pick_project<16, 16, 16>(kind);
-        case 1: return pick_project<8, 16, 16>(kind);
-        default: return pick_project<8, 8, 16>(kind);
-    }
-}
-
-hipError_t init_projbatch_kernels()
-{
-    for (int cfg = 0; cfg < extract_tile_count(); ++cfg)
-        for (int kind = 0; kind < 3; ++kind) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(project_entry_point(cfg, kind)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
-}
+VT_BOX_KERNELS(projbatch, project_tiled<KIND, T::TD, T::TH, T::TW>)
 
 hipError_t launch_project_tiled(int cfg, int interp, const float* src, float* out, double* part, const float* zeros16,
                                 const ExtractEntry* d_tab, const AffineParams& p, int64_t grid, int lds_bytes, hipStream_t stream)
 {
     if (grid <= 0 || grid > 0x7fffffffLL || (p.nTd > 1 && !part)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(project_entry_point(cfg, interp_kind(interp)), dim3((unsigned)grid), dim3(256), lds_bytes, stream,
+    hipLaunchKernelGGL(projbatch_kernels.fn[cfg][interp_kind(interp)], dim3((unsigned)grid), dim3(256), lds_bytes, stream,
                        src, out, part, zeros16, d_tab, p);
     return hipGetLastError();
 }
