@@ -102,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -410,6 +410,37 @@ int vt_volume_backproject_boxes(vt_volume_t* vol, int nb, int n, const float* m4
 int vt_volume_backproject_boxes_f64(vt_volume_t* vol, int nb, int n, const double* m4x4s /* nb x n x 16 */,
                                     const int32_t* planes /* n, or NULL */, const double* weights /* nb x n, or NULL = all 1 */,
                                     int box_d, int box_h, int box_w, float* out /* nb boxes, C order */, int flags);
+
+/* ---- warp: the resident volume resampled through a displacement grid (no reference counterpart on the GPU; the CPU analogue is
+ * scipy.ndimage.map_coordinates, of which affine_transform is the affine special case) ----
+ *     out[v] = sample(src, s(v)),   s(v) = a(v) + u(v)   in float64, for every voxel v = (d, h, w) of an output of out_d x out_h x out_w.
+ * a(v): the float64 fma chain of the pull matrix m4x4 (rows 0..2; NULL = identity), the one vt_volume_extract documents.
+ * u(v): the trilinear interpolation, in float64, of the control grid `grid` (host memory, grid_d x grid_h x grid_w x 3 float32 in C
+ * order): component c of a node is a displacement in source voxels along array axis c.  The nodes span the output corner to corner:
+ * node (i, j, k) sits at output coordinate (i (out_d - 1) / (grid_d - 1), ..).  Per axis either g_k == 1 (constant along that axis) or
+ * 2 <= g_k <= o_k; g == o is a dense field.  The expression is fixed:
+ *     r_k = (g_k - 1) / (o_k - 1) (one float64 division; 0 where g_k == 1),  q_k = v_k * r_k,  c_k = min(floor(q_k), g_k - 2),  f_k = q_k - c_k,
+ *     lerp(f, a, b) = fma(f, b - a, a) per component along axis 2, then axis 1, then axis 0 (where g_k == 1: the node itself).
+ * Inside test: the skirt rule on s (vlo <= s_r < vhi on every axis); outside voxels are written as +0.  Value: the handle's interpolation
+ * at (int)floor(s_r), (float)(s_r - floor(s_r)).  On VT_EDGE_SCIPY handles the pad is folded into the matrix translation, as in
+ * vt_volume_extract; the displacement is additive.
+ * A voxel is a function of (v, m4x4, grid, shapes, source, interpolation): it does not depend on the route its tile took (trilinear
+ * handles: bit for bit; the cubic kinds to rounding only -- the staged route sums the 16 tap rows per column first, the global-memory route
+ * per row first), on host versus device output or on earlier calls.
+ * ONE workgroup per output tile (vt_volume_place's tile for that output shape; last_kernel 20, last_grid = output tiles) loads the nodes
+ * its voxels touch into LDS and bounds its source box by their range.  A tile whose own box fits 96 KiB stages it in LDS; the others, and
+ * tiles whose displacements are beyond (2^20 / (max_k g_k - 1)) voxels, gather from global memory inside the same launch.  VT_FORCE_DIRECT
+ * makes every tile gather; VT_FORCE_TILED is the default route; every other flag but VT_OUT_DEVICE is ignored.  last_lds_dims = the staged
+ * dims of the largest staged tile, (0, 0, 0) when none stages; last_lds_bytes = node block + that box.  The grid is uploaded per call
+ * into a buffer the handle recycles (12 bytes per node).
+ * Bounds (VT_EUNSUPPORTED beyond, decided before any array is read): output tiles < 2^31, nodes x 3 < 2^31, the output as for
+ * vt_volume_place.  Slab handles and handles not yet finalized: VT_EINVAL; VT_STACK handles with a filt_* interpolation: VT_EUNSUPPORTED;
+ * grid dims outside the rule above, non-positive output dims, non-finite matrix entries or grid values, NULL vol / grid / out: VT_EINVAL.
+ * Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  A refusal leaves the handle usable. */
+int vt_volume_warp(vt_volume_t* vol, const float* m4x4 /* or NULL = identity */, const float* grid /* grid_d x grid_h x grid_w x 3 */,
+                   int grid_d, int grid_h, int grid_w, int out_d, int out_h, int out_w, float* out, int flags);
+int vt_volume_warp_f64(vt_volume_t* vol, const double* m4x4 /* or NULL = identity */, const float* grid /* grid_d x grid_h x grid_w x 3 */,
+                       int grid_d, int grid_h, int grid_w, int out_d, int out_h, int out_w, float* out, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

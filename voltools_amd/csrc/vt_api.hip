@@ -279,6 +279,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_place_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_backproject_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_backproject_boxes_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_warp_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -2461,6 +2462,56 @@ int do_backproject_boxes(vt_volume* v, int nb, int n, const MT* m4x4s, const int
     return res.finish();
 }
 
+// The resident volume resampled through a displacement grid: out[v] = sample(src, M.v + u(v)), u the float64 trilinear interpolation of
+// the (gd, gh, gw, 3) float32 grid whose nodes span the (od, oh, ow) output corner to corner (vt_kernels_warp.hip has the expression).
+// m4x4 == nullptr: the identity.  One launch of kernel 20, one workgroup per output tile; the tile is do_place's, a function of (output
+// shape, interpolation).  The table (WarpTable) and the grid behind it travel in the staging vector.  Does not read or change the handle's
+// own output shape.
+int do_warp(vt_volume* v, const double* m4x4, const float* grid, int gd, int gh, int gw, int od, int oh, int ow, float* out, int flags)
+{
+    if (!v || !grid || !out) return fail(VT_EINVAL, "NULL argument");
+    if (refuse_in_plane(v)) return VT_EUNSUPPORTED;
+    int rc = check_shape("output", od, oh, ow);
+    if (rc || (rc = check_whole_volume(v, "warping"))) return rc;
+    const int shape[3] = {od, oh, ow}, g[3] = {gd, gh, gw};
+    for (int k = 0; k < 3; ++k)
+        if (g[k] != 1 && (g[k] < 2 || g[k] > shape[k]))
+            return fail(VT_EINVAL, "grid dims (%d,%d,%d): per axis 1 node, or 2 up to the output's %d x %d x %d", gd, gh, gw, od, oh, ow);
+    // the bounds, before anything of the caller's arrays is read
+    const int64_t node_floats = (int64_t)gd * gh * gw * 3;      // g_k <= o_k, o_d o_h < 2^31: no overflow
+    if (node_floats > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "grid too large (%d x %d x %d nodes)", gd, gh, gw);
+    const BoxTiles t = box_tiles(extract_pick_tile(is_cubic(v->interp), shape, nullptr), od, oh, ow);
+    if (t.count > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "output too large (%lld tiles)", (long long)t.count);
+    const size_t n_out = (size_t)od * oh * ow;                   // < 2^62 by check_shape
+    static const double identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    if (!m4x4) m4x4 = identity;
+    if ((rc = select_device(v)) || (rc = check_finite_matrices(m4x4, 1))) return rc;
+    for (int64_t i = 0; i < node_floats; ++i)
+        if (!std::isfinite(grid[i])) return fail(VT_EINVAL, "grid node %lld component %d is not finite", (long long)(i / 3), (int)(i % 3));
+
+    // the launch's table: WarpTable, then the grid
+    constexpr size_t kTableDoubles = sizeof(WarpTable) / sizeof(double);
+    if ((rc = begin_tables(v, kTableDoubles + ((size_t)node_floats + 1) / 2))) return rc;
+    WarpTable* const wt = reinterpret_cast<WarpTable*>(v->h_batch_m.data());
+    std::memcpy(v->h_batch_m.data() + kTableDoubles, grid, (size_t)node_floats * sizeof(float));
+    double m[12];                                                // fold_matrix on a whole-volume handle: the matrix, plus the pad
+    std::memcpy(m, m4x4, sizeof(m));
+    const double pad = (double)v->edge_pad;
+    m[3] += pad; m[7] += pad; m[11] += pad;
+    const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
+    int L[3], lds_bytes = 0;
+    warp_plan(m, grid, g, shape, t.cfg, is_cubic(v->interp), force_direct, wt, L, &lds_bytes);
+    if (lds_bytes > v->lds_limit) return fail(VT_EUNSUPPORTED, "the launch needs %d bytes of LDS, the device grants %d", lds_bytes, v->lds_limit);
+    const AffineParams p = box_params(v, od, oh, ow, t.nT);
+    record_launch(v, 20, t.T, L, lds_bytes, t.count);
+
+    ResultScope res(v, out, n_out * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open()) || (rc = upload_tables(v))) return rc;
+    VT_HIP(launch_warp(t.cfg, v->interp, v->d_src, res.ptr<float>(), v->d_zeros, reinterpret_cast<const WarpTable*>(v->d_batch_m),
+                       reinterpret_cast<const float*>(v->d_batch_m + kTableDoubles), p, t.count, lds_bytes, v->stream));
+    return res.finish();
+}
+
 // a float32 batch of n matrices in float64
 std::vector<double> widened(const float* m4x4s, int n)
 {
@@ -2873,6 +2924,21 @@ int vt_volume_backproject_boxes_f64(vt_volume_t* v, int nb, int n, const double*
                                     int box_d, int box_h, int box_w, float* out, int flags)
 {
     return do_backproject_boxes(v, nb, n, m4x4s, planes, weights, box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_warp(vt_volume_t* v, const float* m4x4, const float* grid, int grid_d, int grid_h, int grid_w, int out_d, int out_h, int out_w,
+                   float* out, int flags)
+{
+    double m[16];
+    if (m4x4)
+        for (int i = 0; i < 16; ++i) m[i] = (double)m4x4[i];
+    return do_warp(v, m4x4 ? m : nullptr, grid, grid_d, grid_h, grid_w, out_d, out_h, out_w, out, flags);
+}
+
+int vt_volume_warp_f64(vt_volume_t* v, const double* m4x4, const float* grid, int grid_d, int grid_h, int grid_w, int out_d, int out_h,
+                       int out_w, float* out, int flags)
+{
+    return do_warp(v, m4x4, grid, grid_d, grid_h, grid_w, out_d, out_h, out_w, out, flags);
 }
 
 int vt_volume_extract_dot(vt_volume_t* v, int n, const float* m4x4s, const float* tmpl, const float* mask, int box_d, int box_h, int box_w,

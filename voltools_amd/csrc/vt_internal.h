@@ -356,6 +356,32 @@ hipError_t launch_backproject_boxes(int cfg, int interp, const float* src, float
                                     const double* d_wts, int nb, int n, int buf_floats, bool accumulate, const AffineParams& p,
                                     int lds_bytes, hipStream_t stream);
 
+// resampling through a displacement grid (vt_kernels_warp.hip, kind 20): s(v) = M.v + u(v), u the float64 trilinear interpolation of a
+// (gD, gH, gW, 3) float32 control grid whose nodes span the output corner to corner.  One workgroup per output tile loads its nodes into
+// LDS, bounds its source box by their range and stages that box, or gathers from global memory when its own box exceeds kWarpBoxCap.
+constexpr int kWarpScratchFloats = 32;           // LDS in front of the node block: the cross-wave reduction of the node range
+// Bytes of LDS a tile's staged box may take.  With the largest node block (17^3 nodes, 58956 bytes) and the scratch the launch stays
+// below the 160 KiB a workgroup can have; boxes of ordinary fields (<= 48 KiB) leave room for three workgroups per CU.
+constexpr int kWarpBoxCap = 96 * 1024;
+// A tile bounds its source box by the hull of its nodes only while (largest |node component|) x (max_k g_k - 1) <= this (the header of
+// vt_kernels_warp.hip derives the bound on what trilinear extrapolation by an ulp of f can add).
+constexpr double kWarpHullLimit = 1048576.0;
+struct WarpTable {
+    ExtractEntry e;            // folded matrix and tile reach of the launch's tile; tiled = 0: every tile gathers from global memory
+    double r[3];               // (g_k - 1) / (o_k - 1); 0 where g_k == 1
+    double ext[3];             // affine extent of a tile per source axis: sum_k |m[r][k]| (T_k - 1)
+    int32_t g[3];              // nodes per axis
+    int32_t node_floats;       // floats of LDS between the scratch and the staged box (the largest node block, a multiple of 4)
+    int32_t pad_[4];
+};
+static_assert(sizeof(WarpTable) == 272, "the grid follows the table 16-byte aligned");
+// fills *wt and reports the dims of the largest staged box ((0, 0, 0): no tile stages) and the launch's dynamic LDS
+void warp_plan(const double m[12], const float* grid, const int g[3], const int out_shape[3], int cfg, bool cubic, bool force_direct,
+               WarpTable* wt, int L_max[3], int* lds_bytes);
+hipError_t init_warp_kernels();
+hipError_t launch_warp(int cfg, int interp, const float* src, float* out, const float* zeros16, const WarpTable* d_tab, const float* d_grid,
+                       const AffineParams& p, int64_t grid, int lds_bytes, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

@@ -266,3 +266,29 @@ def _box_shape(box_shape) -> Tuple[int, int, int]:
     if len(box) != 3 or not all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) and b > 0 for b in box):
         raise ValueError('box_shape must be three positive ints')
     return tuple(int(b) for b in box)
+
+
+def grid_nodes(grid_shape, output_shape) -> np.ndarray:
+    """Output coordinates of the nodes of a displacement grid (``StaticVolume.warp``): a float64 array ``(gD, gH, gW, 3)`` whose entry
+    ``[i, j, k]`` is ``(i (oD - 1) / (gD - 1), j (oH - 1) / (gH - 1), k (oW - 1) / (gW - 1))`` -- the nodes span the output corner to
+    corner.  An axis with one node (the field is constant along it) reports the middle of the output, ``(o - 1) / 2``.  Per axis either
+    ``g == 1`` or ``2 <= g <= o``.  A caller writes ``displacements = f(grid_nodes(grid_shape, output_shape))``.
+    """
+    try:
+        g = _box_shape(grid_shape)
+        o = _box_shape(output_shape)
+    except ValueError:
+        raise ValueError('grid_shape and output_shape must be three positive ints each')
+    axes = []
+    for gk, ok in zip(g, o):
+        if gk == 1:
+            axes.append(np.array([(ok - 1) / 2.0]))
+        elif 2 <= gk <= ok:
+            axes.append(np.arange(gk, dtype=np.float64) * (ok - 1) / (gk - 1))
+        else:
+            raise ValueError(f'grid_shape {g}: per axis 1 node, or 2 up to the output size {o}')
+    nodes = np.empty(g + (3,), dtype=np.float64)
+    nodes[..., 0] = axes[0][:, None, None]
+    nodes[..., 1] = axes[1][None, :, None]
+    nodes[..., 2] = axes[2][None, None, :]
+    return nodes

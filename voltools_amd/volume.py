@@ -22,6 +22,28 @@ from .utils.matrices import _box_shape
 Vec3 = Union[Tuple[float, float, float], np.ndarray]
 
 
+def _warp_coordinates(disp: np.ndarray, m: np.ndarray, shape) -> np.ndarray:
+    """Source coordinates ``(3, oD, oH, oW)``, float64, of ``StaticVolume.warp``: ``M . v`` plus the trilinear interpolation of the float32
+    grid ``disp`` -- per axis ``q = v (g - 1) / (o - 1)``, cell ``c = min(floor(q), g - 2)``, ``f = q - c``, lerps ``a + f (b - a)`` along
+    axis 2, then 1, then 0 (the order of the GPU kernel; numpy rounds the product and the sum separately, a difference of an ulp)."""
+    u = disp.astype(np.float64)
+    for axis in (2, 1, 0):
+        g, o = u.shape[axis], shape[axis]
+        if g == 1:
+            u = np.repeat(u, o, axis=axis) if o > 1 else u
+            continue
+        q = np.arange(o, dtype=np.float64) * ((g - 1) / (o - 1))
+        c = np.minimum(np.floor(q).astype(np.int64), g - 2)
+        f = (q - c).reshape([-1 if k == axis else 1 for k in range(4)])
+        a, b = np.take(u, c, axis=axis), np.take(u, c + 1, axis=axis)
+        u = a + f * (b - a)
+    d, h, w = (np.arange(n, dtype=np.float64) for n in shape)
+    coords = np.empty((3,) + tuple(shape), dtype=np.float64)
+    for r in range(3):
+        coords[r] = (m[r, 0] * d[:, None, None] + (m[r, 1] * h[None, :, None] + (m[r, 2] * w[None, None, :] + m[r, 3]))) + u[..., r]
+    return coords
+
+
 class StaticVolume:
     """For StaticVolume transforms the boolean reshape cannot be given as an argument."""
 
@@ -249,6 +271,70 @@ class StaticVolume:
         _native.check(rc, 'vt_volume_extract')
         if profile:
             print(f'{n} boxes extracted in {self.timer_stop():.3f}ms')
+        return result
+
+    # -- resampling through a displacement grid (extension: what scipy.ndimage.map_coordinates is to affine_transform) ----
+    def warp(self, displacements, matrix=None, output_shape=None, profile: bool = False, output=None, *,
+             _flags: int = 0) -> Union[np.ndarray, None]:
+        """The volume resampled through a map that need not be affine: ``out[v] = sample(src, M . v + u(v))`` for every voxel ``v = (d, h,
+        w)`` of an output of shape ``output_shape`` (default: the volume's).  ``displacements`` is a control grid ``(gD, gH, gW, 3)`` of
+        displacement vectors in source voxels along array axes 0, 1, 2, taken as float32; its nodes span the output corner to corner
+        (``utils.grid_nodes``), ``u(v)`` is their trilinear interpolation in float64.  Per axis either one node (constant along that axis) or
+        2 up to the output size; a grid of the output's shape is a dense field.  ``matrix`` is a 4 x 4 pull matrix, None for the identity;
+        float64 keeps its precision, anything else is taken as float32.  Voxels that map outside the volume are 0.  Returns a float32
+        array of ``output_shape``, or fills ``output`` of that shape (numpy, ``vt.empty`` device array, torch-ROCm tensor) and returns None
+        on a GPU device.  ``device='cpu'`` evaluates the same float64 coordinates in numpy and hands them to
+        ``scipy.ndimage.map_coordinates``."""
+        shape = _box_shape(self.shape if output_shape is None else output_shape)
+        disp = np.asarray(displacements)
+        if disp.ndim != 4 or disp.shape[3] != 3:
+            raise ValueError('displacements must have shape (gD, gH, gW, 3)')
+        if not all(g == 1 or 2 <= g <= o for g, o in zip(disp.shape[:3], shape)):
+            raise ValueError(f'displacements of grid shape {disp.shape[:3]}: per axis 1 node, or 2 up to the output size {shape}')
+        disp = np.ascontiguousarray(disp, dtype=np.float32)
+        if matrix is not None:
+            m = np.asarray(matrix)
+            if m.shape != (4, 4):
+                raise ValueError('matrix must have shape (4, 4)')
+            m = np.ascontiguousarray(m, dtype=np.float64 if m.dtype == np.float64 else np.float32)
+        else:
+            m = None
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            data = self.data
+            if prefilter:
+                data = spline_filter(data, order, output=np.float64, mode='constant')
+            t_start = time.time()
+            coords = _warp_coordinates(disp, np.eye(4) if m is None else m.astype(np.float64), shape)
+            res = map_coordinates(data, coords, order=order, mode='constant', cval=0, prefilter=False)
+            res = res.astype(self.data.dtype if np.issubdtype(self.data.dtype, np.floating) else np.float64, copy=False)
+            if profile:
+                print(f'warp finished in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        mptr = None if m is None else m.ctypes.data
+        if m is not None and m.dtype == np.float64:
+            rc = self._lib.vt_volume_warp_f64(self._handle, mptr, disp.ctypes.data, *disp.shape[:3], *shape, ptr, flags)
+        else:
+            rc = self._lib.vt_volume_warp(self._handle, mptr, disp.ctypes.data, *disp.shape[:3], *shape, ptr, flags)
+        _native.check(rc, 'vt_volume_warp')
+        if profile:
+            print(f'warp finished in {self.timer_stop():.3f}ms')
         return result
 
     def extract_at(self, positions, rotations=None, box_shape=None, rotation_units: str = 'deg',
