@@ -9,7 +9,9 @@ the header of vt_kernels_warp.hip and sharing nothing with the library:
   * the skirt rule -0.5 <= s_r < dim_r - 0.5 on those coordinates;
   * for filt_* the coefficients of prefilter_model.prefilter_f64;
   * the planning rule: per output tile the node sub-block, its per-component range, the staged dims (extract_box_dims' formula with the
-    extent grown by umax - umin), the origin, and whether the tile stages (box <= BOX_CAP, hull bound granted) or gathers.
+    extent grown by umax - umin), the origin, and whether the tile stages (box <= BOX_CAP, hull bound granted) or gathers;
+  * which voxels the kernel samples (kernel_inside: 'zero' tiles none, `whole` tiles all, the others by the skirt rule), with the
+    switches of three wrong kernels that tests/test_warp_lattice_host.py argues with.
 
 The interpolation arithmetic is float64 throughout; what the library does in float32 is covered by the tolerances of the tests."""
 import numpy as np
@@ -119,12 +121,22 @@ def sample(vol, s, interp):
                     val += wgt * _tap(vol, i[0] + a, i[1] + b, i[2] + c)
         return val
     wz, wy, wx = _weights(f[0]), _weights(f[1]), _weights(f[2])
+    # the 64 taps of _tap, fetched from a copy of the volume inside a shell of zeros: an index that leaves the volume is clipped onto
+    # the shell (the same values as _tap's select, with one index computation per axis and offset instead of one per tap)
+    D, H, W = vol.shape
+    shell = np.zeros((D + 2, H + 2, W + 2), np.float64)
+    shell[1:-1, 1:-1, 1:-1] = vol
+    flat = shell.reshape(-1)
+    iz = [np.clip(i[0] + a, 0, D + 1) * ((H + 2) * (W + 2)) for a in range(4)]          # (i - 1 + a) + 1: the shell's offset
+    iy = [np.clip(i[1] + b, 0, H + 1) * (W + 2) for b in range(4)]
+    ix = [np.clip(i[2] + c, 0, W + 1) for c in range(4)]
     val = np.zeros(s.shape[1:], np.float64)
     for a in range(4):
         for b in range(4):
             row = np.zeros(s.shape[1:], np.float64)
+            zy = iz[a] + iy[b]
             for c in range(4):
-                row += wx[c] * _tap(vol, i[0] - 1 + a, i[1] - 1 + b, i[2] - 1 + c)
+                row += wx[c] * flat[zy + ix[c]]
             val += (wz[a] * wy[b]) * row
     return val
 
@@ -181,9 +193,10 @@ class Plan:
     pass
 
 
-def plan(m, grid, out_shape, interp, force_direct=False):
+def plan(m, grid, out_shape, interp, force_direct=False, origin_without_umin=False):
     """The launch plan: .cfg, .tile, .nT, .staged (bool per tile), .dims / .origin (int per tile x 3; zeros where not staged), .cells /
-    .nodes (first cell / node count per tile x 3), .lds_dims (the launch's last_lds_dims), .node_floats, .lds_bytes."""
+    .nodes (first cell / node count per tile x 3), .lds_dims (the launch's last_lds_dims), .node_floats, .lds_bytes.
+    `origin_without_umin` is a MUTATION (tests/test_warp_lattice_host.py): the origin a wrong kernel would take from base + neg alone."""
     m = np.eye(4) if m is None else np.asarray(m, np.float64)
     grid = np.asarray(grid, np.float32)
     g = grid.shape[:3]
@@ -237,7 +250,7 @@ def plan(m, grid, out_shape, interp, force_direct=False):
                 o = []
                 for row in range(3):
                     base = float(_fma(m[row, 0], t0[0], _fma(m[row, 1], t0[1], _fma(m[row, 2], t0[2], m[row, 3]))))
-                    lo = base + neg[row] + float(umin[row])
+                    lo = base + neg[row] + (0.0 if origin_without_umin else float(umin[row]))
                     o.append(int(np.floor(lo - BOX_MARGIN)) - halo)
                 o[2] &= ~3
                 p.origin[a, b, c] = o
@@ -265,6 +278,43 @@ def tile_outcome(p, m, src_shape):
             any_valid = any_valid and hi >= -0.5 - TILE_MARGIN and lo < src_shape[row] - 0.5 + TILE_MARGIN
         out[idx] = 'zero' if (hull and not any_valid) else ('stage' if p.staged[idx] else 'direct')
     return out
+
+
+def whole_tiles(p, m, src_shape, margin=TILE_MARGIN):
+    """Per tile: staged AND [base + neg + umin, base + pos + umax] inside the valid interval by `margin` on every axis -- the tiles whose
+    voxels skip the per-voxel inside test.  margin=0.0 is a MUTATION: `whole` by a bare comparison."""
+    m = np.eye(4) if m is None else np.asarray(m, np.float64)
+    T = p.tile
+    out = np.zeros(p.nT, bool)
+    for idx in np.ndindex(*p.nT):
+        if not p.staged[idx]:
+            continue
+        t0 = [idx[k] * T[k] for k in range(3)]
+        ok = True
+        for row in range(3):
+            base = float(_fma(m[row, 0], t0[0], _fma(m[row, 1], t0[1], _fma(m[row, 2], t0[2], m[row, 3]))))
+            lo = base + p.neg[row] + float(p.umin[idx][row])
+            hi = base + p.pos[row] + float(p.umax[idx][row])
+            ok = ok and lo >= -0.5 + margin and hi < src_shape[row] - 0.5 - margin
+        out[idx] = ok
+    return out
+
+
+def kernel_inside(p, m, s, src_shape, out_shape, margin=TILE_MARGIN, s_test=None):
+    """The mask of voxels the kernel SAMPLES under plan p: none in a 'zero' tile, all in a whole tile, elsewhere the skirt rule on
+    `s_test` (default s, the definition).  With the defaults it must equal inside(s, src_shape) -- that is what kTileMargin and the hull
+    bound are for; `margin` and `s_test` are the switches of two wrong kernels."""
+    T = p.tile
+    mask = inside(s if s_test is None else s_test, src_shape).copy()
+    what = tile_outcome(p, m, src_shape)
+    whole = whole_tiles(p, m, src_shape, margin)
+    for idx in np.ndindex(*p.nT):
+        sl = tuple(slice(idx[k] * T[k], min((idx[k] + 1) * T[k], out_shape[k])) for k in range(3))
+        if what[idx] == 'zero':
+            mask[sl] = False
+        elif whole[idx]:
+            mask[sl] = True
+    return mask
 
 
 def violations(p, s, out_shape, interp):
