@@ -44,6 +44,33 @@ def is_cubic(interp):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Q32.32 (vt_device.h: Fx, to_fx, fx_step; the host's split of a step: plan_prepare, extract_fill_entry)
+# ---------------------------------------------------------------------------------------------------
+def fx_inc(step):
+    """(inc_hi, inc_lo) of a float64 step: floor and the fraction ROUNDED to the nearest unit of 2^-32."""
+    step = float(step)
+    fl = np.floor(step)
+    hi = int(fl) if abs(step) < 2.0e9 else 0
+    scaled = (step - fl) * _TWO32 + 0.5
+    lo = int(min(4294967295.0, np.floor(scaled)))
+    if scaled >= _TWO32:
+        lo, hi = 0, hi + 1
+    return hi, lo
+
+
+def to_fx(s):
+    """(hi as int64, lo as uint64) of float64 coordinates: floor and the fraction TRUNCATED, as the device's (unsigned) conversion."""
+    fl = np.floor(s)
+    return fl.astype(np.int64), ((s - fl) * _TWO32).astype(np.uint64)
+
+
+def fx_step(hi, lo, inc_hi, inc_lo):
+    """One step: the low words add modulo 2^32, the carry goes to the high word."""
+    lo = lo + np.uint64(inc_lo)
+    return hi + inc_hi + (lo >> np.uint64(32)).astype(np.int64), lo & np.uint64(0xFFFFFFFF)
+
+
+# ---------------------------------------------------------------------------------------------------
 # the planner
 # ---------------------------------------------------------------------------------------------------
 def extract_box_dims(m, T, halo2, params=PARAMS):
@@ -93,13 +120,7 @@ def extract_fill_entry(m, cfg, cubic, lds_cap=LDS_CAP, params=PARAMS):
                 p += x
         neg.append(n)
         pos.append(p)
-        step = float(m[r][0])
-        fl = np.floor(step)
-        hi = int(fl) if abs(step) < 2.0e9 else 0
-        scaled = (step - fl) * _TWO32 + 0.5
-        lo = int(min(4294967295.0, np.floor(scaled)))
-        if scaled >= _TWO32:
-            lo, hi = 0, hi + 1
+        hi, lo = fx_inc(m[r][0])
         inc_hi.append(hi)
         inc_lo.append(lo)
     L = extract_box_dims(m, T, 2 if cubic else 0, params)
@@ -181,9 +202,9 @@ def _march(m, box, T, entry, cubic, src_shape, params, td_range):
     for r in range(3):
         s = _fma(m[r][0], i0, _fma(m[r][1], j, _fma(m[r][2], kw, b[r].reshape(T5))))
         s = np.broadcast_to(s, full)
-        fl = np.floor(s)
-        c_hi.append(fl.astype(np.int64))
-        c_lo.append(((s - fl) * _TWO32).astype(np.uint64))          # truncation, as the device's (unsigned) conversion
+        hi, lo = to_fx(s)
+        c_hi.append(hi)
+        c_lo.append(lo)
     ext_lo = [None] * 3
     ext_hi = [None] * 3
     flat_lo, flat_hi = None, None
@@ -211,10 +232,7 @@ def _march(m, box, T, entry, cubic, src_shape, params, td_range):
             flat_lo = fa if flat_lo is None else min(flat_lo, fa)
             flat_hi = fz if flat_hi is None else max(flat_hi, fz)
         for r in range(3):
-            lo = c_lo[r] + np.uint64(entry['inc_lo'][r])
-            carry = (lo >> np.uint64(32)).astype(np.int64)
-            c_hi[r] = c_hi[r] + entry['inc_hi'][r] + carry
-            c_lo[r] = lo & np.uint64(0xFFFFFFFF)
+            c_hi[r], c_lo[r] = fx_step(c_hi[r], c_lo[r], entry['inc_hi'][r], entry['inc_lo'][r])
     return ext_lo, ext_hi, flat_lo, flat_hi, int(np.prod(tshape)), int(any_valid.sum()), int(whole.sum()), below
 
 

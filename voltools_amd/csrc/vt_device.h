@@ -148,9 +148,10 @@ __device__ __forceinline__ bool blocked_tile(int t, int nTd, int nTh, int nTw, i
 // The kernels that place a staged box by that bounding box keep kBoxMargin for it.
 struct Fx { int hi; unsigned lo; };
 
-// Origin and extent margin of the box kernels (kinds 11-16): o = floor(lo - kBoxMargin) - HALO puts every tap index at
+// Origin and extent margin of the box kernels (kinds 11-16) and of the general-matrix kernels (kinds 2, 9, 6; the test build's 3, 4, 5,
+// whose per-pixel fma chain can round below `base + neg`): o = floor(lo - kBoxMargin) - HALO puts every tap index at
 // or above 0 although the fixed-point coordinate of a voxel that sits exactly on floor(lo) may have drifted below it;
-// extract_box_dims sizes the box for an extent of ext + 2 kBoxMargin, which covers the lowered origin and the same
+// extract_box_dims and the planners of vt_plan.hip size the box for an extent of ext + 2 kBoxMargin, which covers the lowered origin and the same
 // drift at the upper end.  Any value from 2^-28 up that is small against a voxel would do.  The shift is by a whole
 // voxel, so fractions -- and results -- are unchanged.  
 constexpr double kBoxMargin = 0x1p-24;

@@ -81,10 +81,11 @@ __global__ __launch_bounds__(256) void affine_tiled(const float* __restrict__ sr
 
     // integer origin of the staged box (finite and small here: the tile intersects the valid interval and
     // its extent was bounded on the host).  x origin aligned down to 16 bytes: rows of the resident source
-    // are 16-byte aligned (pitch % 4 == 0).
+    // are 16-byte aligned (pitch % 4 == 0).  kBoxMargin (vt_device.h): a voxel that sits exactly on floor(lo) may
+    // reach its last plane with a Q32.32 coordinate a few units of 2^-32 below it.
     int o[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r]) - HALO;
+    for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;
     o[2] &= ~3;
 
     const int Lx = p.Lx, Ly = p.Ly, Lz = p.Lz;
@@ -229,8 +230,8 @@ __global__ __launch_bounds__(256) void affine_tiled_zsep(const float* __restrict
 
     int o[3];
     o[0] = d0 + p.zoff - HALO;
-    o[1] = (int)floor(lo[1]) - HALO;
-    o[2] = ((int)floor(lo[2]) - HALO) & ~3;
+    o[1] = (int)floor(lo[1] - kBoxMargin) - HALO;          // (vt_device.h: here the tile's `base + neg` against a pixel's own fma chain)
+    o[2] = ((int)floor(lo[2] - kBoxMargin) - HALO) & ~3;
     const int Lx = p.Lx, Ly = p.Ly;
     stage_box(lds, src, zeros16, p, o, NPL, Ly, Lx, tid);
     __syncthreads();

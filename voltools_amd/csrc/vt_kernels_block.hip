@@ -375,7 +375,7 @@ __device__ __forceinline__ void affine_block_body(const float* __restrict__ src,
 
         int o[3];
 #pragma unroll
-        for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r]) - HALO;
+        for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;      // (vt_device.h: kBoxMargin)
         o[2] &= ~3;
         const bool box_inside = o[0] >= 0 && o[1] >= 0 && o[2] >= 0 && o[0] + Lz <= p.sD && o[1] + Ly <= p.sH && o[2] + p.Lx_used <= p.sP;
 

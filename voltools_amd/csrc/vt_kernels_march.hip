@@ -161,8 +161,8 @@ __global__ __launch_bounds__(NT) void affine_march_zsep(const float* __restrict_
         return;
     }
 
-    const int o1 = (int)floor(lo[1]) - HALO;
-    const int o2 = ((int)floor(lo[2]) - HALO) & ~3;
+    const int o1 = (int)floor(lo[1] - kBoxMargin) - HALO;      // (vt_device.h: here the tile's `base + neg` against a pixel's own fma chain)
+    const int o2 = ((int)floor(lo[2] - kBoxMargin) - HALO) & ~3;
     const int Ly = p.Ly;                          // <= kRowsMax
 
     // ---- per-pixel tap geometry ----
@@ -491,8 +491,8 @@ __global__ __launch_bounds__(NT) VT_ZPAIR_OCC void affine_march_zpair(const floa
         return;
     }
 
-    const int o1 = (int)floor(lo[1]) - HALO;
-    const int o2 = ((int)floor(lo[2]) - HALO) & ~1;            // 16-byte vectors hold 2 positions x 2 planes
+    const int o1 = (int)floor(lo[1] - kBoxMargin) - HALO;
+    const int o2 = ((int)floor(lo[2] - kBoxMargin) - HALO) & ~1;            // 16-byte vectors hold 2 positions x 2 planes
     const int Ly = p.Ly, Lx = p.Lx;                              // Lx in positions, even
     const int slot_floats = p.slot_floats;
     const bool box_mode = (p.flags & (1 << 20)) != 0;

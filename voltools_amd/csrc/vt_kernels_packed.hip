@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256, (KIND == 0 ? 3 : 2)) void affine_tiled_packed(
         } else {
             int o[3];
 #pragma unroll
-            for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r]) - HALO;
+            for (int r = 0; r < 3; ++r) o[r] = (int)floor(lo[r] - kBoxMargin) - HALO;      // (vt_device.h: kBoxMargin)
             o[2] &= ~3;
             double b[3];
 #pragma unroll

@@ -226,7 +226,9 @@ int quad_row_stride(const double m[12], int th, int tw, double* factor, bool lan
 }
 
 // Source extent of an in-plane TH x TW tile under rows 1, 2 of the matrix (+ taps), in rows / columns; false when absurd.
-bool inplane_box(const double m[12], int th, int tw, int halo2, int L[3])
+// `margin`: 2 kBoxMargin for the kernels that lower their origin by kBoxMargin (the test build's marching kernels, which index a box);
+// 0 for the plane-quad kernel, which clamps its row index and takes its columns from the pixels' own indices.
+bool inplane_box(const double m[12], int th, int tw, int halo2, int L[3], double margin = 0.0)
 {
     const int T[3] = {1, th, tw};
     L[0] = 0;
@@ -234,7 +236,7 @@ bool inplane_box(const double m[12], int th, int tw, int halo2, int L[3])
         double ext = 0;
         for (int k = 1; k < 3; ++k) ext += std::fabs(m[4 * r + k]) * (T[k] - 1);
         if (!(ext < 4096.0)) return false;
-        L[r] = (int)std::floor(ext) + 3 + halo2;
+        L[r] = (int)std::floor(ext + margin) + 3 + halo2;
     }
     return true;
 }
@@ -459,7 +461,7 @@ bool zpair_pick_tile(PlanCtx& c)
         if (v->tune.la > 0) la = std::min(3, v->tune.la);
         const int vec_max = nt * march_max_it();
         int L[3];
-        if (!inplane_box(m, th, tw, c.halo2, L)) continue;
+        if (!inplane_box(m, th, tw, c.halo2, L, 2.0 * kBoxMargin)) continue;
         L[2] = (L[2] + 1 + 1) & ~1;                      // origin aligned down by up to 1 position, even width
         // boxes (stride padding fetched from the zero vector) vs packed spans [measured]: 512^3 sweep mean 0.292 vs
         // 0.312 ms, 1024^3 2.25-2.33 vs 2.28-2.38 ms -> boxes; VT_MARCH_BOX=0 selects packed spans
@@ -568,7 +570,7 @@ bool march_pick_tile(PlanCtx& c)
         if (v->tune.la > 0) la = v->tune.la;
         const int vec_max = nt * march_max_it();
         int L[3];
-        if (!inplane_box(m, th, tw, c.halo2, L) || L[1] > march_rows_max()) continue;
+        if (!inplane_box(m, th, tw, c.halo2, L, 2.0 * kBoxMargin) || L[1] > march_rows_max()) continue;
         int rows = 0;
         const int vecs = estimate_packed_vectors(m, th, tw, c.cubic ? 1 : 0, L[1] + 1, &rows);
         if (vecs > vec_max || rows > march_rows_max()) continue;
@@ -671,7 +673,7 @@ bool pick_box_tile(PlanCtx& c, double* bpv)
             double ext = 0;
             for (int k = 0; k < 3; ++k) ext += std::fabs(m[4 * r + k]) * (T[k] - 1);
             if (!(ext < 4096.0)) { ok = false; break; }
-            L[r] = (int)std::floor(ext) + 3 + c.halo2;       // floor(hi)-floor(lo) <= floor(ext)+1, +1 upper tap, +1 slack
+            L[r] = (int)std::floor(ext + 2.0 * kBoxMargin) + 3 + c.halo2;      // floor(hi + drift) - floor(lo - kBoxMargin) <= floor(ext + 2 kBoxMargin) + 1, + 1 upper tap, + 1 slack
         }
         if (!ok) continue;
         if (c.zsep) L[0] = T[0] + 1 + c.halo2;               // exactly the planes d0+zoff-halo .. d0+TD+zoff+halo
@@ -766,7 +768,7 @@ void pick_packed_tile(PlanCtx& c, const double inv[9], PackedChoice* out)
             g.ext[r] = ext;
             // (span kernel: its box origin lies 4e-9 below the tile's lowest coordinate and its Q32.32 coordinates carry 2e-9 of rounding,
             //  vt_kernels_span.hip: fx64 -- an extent within 1e-8 of an integer needs the next row as well)
-            L[r] = (int)std::floor(ext + (span ? 1.0e-8 : 0.0)) + 3 + c.halo2;
+            L[r] = (int)std::floor(ext + (span ? 1.0e-8 : 2.0 * kBoxMargin)) + 3 + c.halo2;
         }
         if (!ok) continue;
         L[2] = (L[2] + 3 + 3) & ~3;
@@ -939,7 +941,7 @@ bool plan_block_th(PlanCtx& c, int th)
         double ext = 0;
         for (int k = 0; k < 3; ++k) ext += std::fabs(m[4 * r + k]) * (T[k] - 1);
         if (!(ext < 256.0)) return false;
-        L[r] = (int)std::floor(ext) + 3 + c.halo2;           // floor(hi)-floor(lo) <= floor(ext)+1, +1 upper tap, +1 slack
+        L[r] = (int)std::floor(ext + 2.0 * kBoxMargin) + 3 + c.halo2;      // (as pick_box_tile)
     }
     const int lx_used = (L[2] + 3 + 3) & ~3;                 // origin aligned down by up to 3, whole vectors
     // Row stride: the smallest of 28 / 36 floats that holds the box row -- or 32 where the box then exceeds the staging budget
