@@ -82,8 +82,8 @@ enum vt_create_flags {
     VT_SRC_DEFERRED = 8,     /* `data` may be NULL: the resident window starts zero-filled, is filled plane range by plane
                                 range with vt_volume_upload_planes and becomes usable with vt_volume_finalize              */
     VT_STACK = 32            /* the planes are independent images (a tilt series) for vt_volume_backproject: filt_* interpolations prefilter
-                                along axes 2 and 1 only, and such a handle (in-plane coefficients) refuses every other sampling entry
-                                point with VT_EUNSUPPORTED.  With the other interpolations the flag changes nothing.  Not together with
+                                along axes 2 and 1 only, and such a handle (in-plane coefficients) refuses every sampling entry
+                                point but the back-projections and vt_volume_affine_stack with VT_EUNSUPPORTED.  With the other interpolations the flag changes nothing.  Not together with
                                 VT_EDGE_SCIPY, a slab window or VT_SRC_DEFERRED (VT_EUNSUPPORTED).                          */
 };
 
@@ -102,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -410,6 +410,39 @@ int vt_volume_backproject_boxes(vt_volume_t* vol, int nb, int n, const float* m4
 int vt_volume_backproject_boxes_f64(vt_volume_t* vol, int nb, int n, const double* m4x4s /* nb x n x 16 */,
                                     const int32_t* planes /* n, or NULL */, const double* weights /* nb x n, or NULL = all 1 */,
                                     int box_d, int box_h, int box_w, float* out /* nb boxes, C order */, int flags);
+
+/* ---- per-image 2-D transforms of a resident stack: a resident stack in, a stack out -- each tilt's alignment (shift, in-plane rotation,
+ * magnification) before reconstruction, movie frames shifted onto each other, every image resampled onto another grid.  The handle holds
+ * the stack (T, H, W) as for vt_volume_backproject.  m4x4s: n x 16 pull matrices, planes: n image indices inside [0, T), or NULL for
+ * planes[i] = i (then n must equal T), weights: n float64, or NULL for all 1.  out: n images of out_h x out_w float32 in C order (host, or
+ * device with VT_OUT_DEVICE).  For output pixel (h, w) of output image i
+ *     y = fma(M_i[1,1], h, fma(M_i[1,2], w, M_i[1,3]))        float64
+ *     x = fma(M_i[2,1], h, fma(M_i[2,2], w, M_i[2,3]))
+ *     out[i, h, w] = float32(weighted_add(+0.0, w_i, B))   if -0.5 <= y < H - 0.5 and -0.5 <= x < W - 0.5, else +0
+ * with B the float32 value of the handle's interpolation taken in TWO dimensions in image planes[i] at ((int)floor(y), (float)(y -
+ * floor(y))), the same for x: bilinear, or the 4 x 4 cubic B-spline with the weights of the handle's 3-D kind; taps outside the image
+ * read 0.  weighted_add(a, w, v) = a + w * double(v) with both roundings, vt_volume_place's accumulation step.  This is
+ * vt_volume_backproject's definition for one entry and an output of depth 1.  Row 0, row 3 and column 0 of a matrix are ignored.
+ * Image i is a fixed expression of (M_i, planes[i], w_i, source, (out_h, out_w), interpolation, route): it does not depend on n, on the
+ * other entries, on its place in the batch, on host versus device output or on earlier calls.  A linear handle writes the same bits on
+ * both routes; with VT_FORCE_DIRECT every interpolation writes the bits of vt_volume_backproject(vol, 1, M_i, &planes[i], &w_i, 1, out_h,
+ * out_w, .., VT_FORCE_DIRECT).
+ * ONE workgroup per (entry, 2-D output tile) (last_kernel 21, last_grid = n x tiles, entry-major so that the tiles of an image share an
+ * XCD's L2) stages ONE image patch in LDS and takes one sample per pixel, coordinates by the chain above.  last_tile = (1, TH, TW), 32 x
+ * 32 or 16 x 16, a function of (out_h, out_w, interpolation).  An entry whose patch, cubic halo included, exceeds 32 KiB gathers from
+ * global memory inside the same launch; that follows from the entry and the output shape alone, the largest staged patch of the batch
+ * only sizes the allocation: last_lds_dims = (1, Ly, Lx) of that patch, (0, 0, 0) when no entry stages, last_lds_bytes = 4 Ly Lx.
+ * VT_FORCE_DIRECT makes every entry gather, VT_FORCE_TILED selects the default; every other flag but VT_OUT_DEVICE is ignored.  Device
+ * memory beyond the source: n x 200 bytes of tables in a buffer the handle recycles.
+ * Bounds (VT_EUNSUPPORTED beyond): n x tiles < 2^31, an image as for vt_volume_backproject, n x image bytes within size_t.
+ * Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  Slab handles and handles not yet
+ * finalized: VT_EINVAL; filt_* without VT_STACK and VT_EDGE_SCIPY handles: VT_EUNSUPPORTED; n <= 0, non-positive dims, non-finite matrix
+ * entries or weights, a plane index outside [0, T), planes == NULL with n != T, NULL vol / m4x4s / out: VT_EINVAL.  A refusal leaves the
+ * handle usable. */
+int vt_volume_affine_stack(vt_volume_t* vol, int n, const float* m4x4s, const int32_t* planes /* n, or NULL */,
+                           const double* weights /* n, or NULL = all 1 */, int out_h, int out_w, float* out, int flags);
+int vt_volume_affine_stack_f64(vt_volume_t* vol, int n, const double* m4x4s, const int32_t* planes /* n, or NULL */,
+                               const double* weights /* n, or NULL = all 1 */, int out_h, int out_w, float* out, int flags);
 
 /* ---- warp: the resident volume resampled through a displacement grid (no reference counterpart on the GPU; the CPU analogue is
  * scipy.ndimage.map_coordinates, of which affine_transform is the affine special case) ----

@@ -2462,6 +2462,56 @@ int do_backproject_boxes(vt_volume* v, int nb, int n, const MT* m4x4s, const int
     return res.finish();
 }
 
+// n images of shape (oh, ow) from the handle's stack, image i from image planes[i] under rows 1 and 2 of matrix i: what do_backproject
+// writes for that single entry at an output of depth 1 (to rounding on the staged cubic routes, bit for bit with VT_FORCE_DIRECT), in one
+// launch of kernel 21 (vt_kernels_stackaffine.hip), n x tiles workgroups.  The tile is a function of (image shape, interpolation);
+// whether an entry stages follows from that entry, the image shape and kStackAffinePatchCap.  The tables are n entries, then n weights
+// (nullptr: ones).  MT: float or double matrices.  Does not read or change the handle's own output shape.
+template <typename MT>
+int do_affine_stack(vt_volume* v, int n, const MT* m4x4s, const int32_t* planes, const double* weights, int oh, int ow, float* out, int flags)
+{
+    if (!v || !m4x4s || !out) return fail(VT_EINVAL, "NULL argument");
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_shape("output", 1, oh, ow)) || (rc = check_backproject_handle(v))) return rc;
+    // the bounds, before anything of the caller's arrays is read
+    const bool cubic = is_cubic(v->interp);
+    const int cfg = stack_affine_pick_tile(cubic, oh, ow);
+    int T[3] = {1, 0, 0};
+    stack_affine_tile(cfg, &T[1], &T[2]);
+    const int nT[3] = {1, (oh + T[1] - 1) / T[1], (ow + T[2] - 1) / T[2]};
+    const int64_t tiles = (int64_t)nT[1] * nT[2];
+    if (tiles * n > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "grid too large (%d images x %lld tiles)", n, (long long)tiles);
+    const size_t image = (size_t)oh * ow;                  // < 2^31 by check_shape
+    if (image > (SIZE_MAX / sizeof(float)) / (size_t)n) return fail(VT_EUNSUPPORTED, "output too large (%d images)", n);
+    if ((rc = select_device(v)) || (rc = check_finite_matrices(m4x4s, (size_t)n)) || (rc = check_finite_weights(weights, (size_t)n)) ||
+        (rc = check_planes(v, n, planes, "")))
+        return rc;
+
+    const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
+    if ((rc = begin_tables(v, (size_t)n * (kEntryDoubles + 1)))) return rc;
+    ExtractEntry* const e = host_entries(v);
+    double* const w = v->h_batch_m.data() + kEntryDoubles * (size_t)n;
+    int L[3] = {0, 0, 0};
+    int64_t largest = 0;
+    for (int i = 0; i < n; ++i) {
+        const MT* a = m4x4s + 16 * (size_t)i;
+        const double rows[8] = {(double)a[4], (double)a[5], (double)a[6], (double)a[7], (double)a[8], (double)a[9], (double)a[10], (double)a[11]};
+        stack_affine_fill_entry(rows, planes ? planes[i] : i, cfg, cubic, oh, ow, force_direct, &e[i]);
+        const int64_t patch = (int64_t)e[i].Ly * e[i].Lx;
+        if (e[i].tiled && patch > largest) { largest = patch; L[0] = 1; L[1] = e[i].Ly; L[2] = e[i].Lx; }
+        w[i] = weights ? weights[i] : 1.0;
+    }
+    const int lds_bytes = (int)(largest * 4);
+    const AffineParams p = box_params(v, 1, oh, ow, nT);
+    record_launch(v, 21, T, L, lds_bytes, tiles * n);
+
+    ResultScope res(v, out, image * (size_t)n * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open()) || (rc = upload_tables(v))) return rc;
+    VT_HIP(launch_stack_affine(cfg, v->interp, v->d_src, res.ptr<float>(), v->d_zeros, device_entries(v), v->d_batch_m + kEntryDoubles * (size_t)n,
+                               n, p, lds_bytes, v->stream));
+    return res.finish();
+}
+
 // The resident volume resampled through a displacement grid: out[v] = sample(src, M.v + u(v)), u the float64 trilinear interpolation of
 // the (gd, gh, gw, 3) float32 grid whose nodes span the (od, oh, ow) output corner to corner (vt_kernels_warp.hip has the expression).
 // m4x4 == nullptr: the identity.  One launch of kernel 20, one workgroup per output tile; the tile is do_place's, a function of (output
@@ -2924,6 +2974,18 @@ int vt_volume_backproject_boxes_f64(vt_volume_t* v, int nb, int n, const double*
                                     int box_d, int box_h, int box_w, float* out, int flags)
 {
     return do_backproject_boxes(v, nb, n, m4x4s, planes, weights, box_d, box_h, box_w, out, flags);
+}
+
+int vt_volume_affine_stack(vt_volume_t* v, int n, const float* m4x4s, const int32_t* planes, const double* weights, int out_h, int out_w,
+                           float* out, int flags)
+{
+    return do_affine_stack(v, n, m4x4s, planes, weights, out_h, out_w, out, flags);
+}
+
+int vt_volume_affine_stack_f64(vt_volume_t* v, int n, const double* m4x4s, const int32_t* planes, const double* weights, int out_h, int out_w,
+                               float* out, int flags)
+{
+    return do_affine_stack(v, n, m4x4s, planes, weights, out_h, out_w, out, flags);
 }
 
 int vt_volume_warp(vt_volume_t* v, const float* m4x4, const float* grid, int grid_d, int grid_h, int grid_w, int out_d, int out_h, int out_w,

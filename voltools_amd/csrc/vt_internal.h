@@ -382,6 +382,19 @@ hipError_t init_warp_kernels();
 hipError_t launch_warp(int cfg, int interp, const float* src, float* out, const float* zeros16, const WarpTable* d_tab, const float* d_grid,
                        const AffineParams& p, int64_t grid, int lds_bytes, hipStream_t stream);
 
+// every image of the stack under its own 2-D affine map (vt_kernels_stackaffine.hip, kind 21): one workgroup per (entry, 2-D output tile),
+// grid = n x tiles entry-major; an entry's rows 1 and 2 map pixel (h, w) of output image i into image (int)m[3].  An entry stages ONE
+// patch of Ly x Lx floats, or gathers from global memory when that patch exceeds kStackAffinePatchCap.
+// Bytes of LDS a staged patch may take: five workgroups (20 waves) per CU by LDS at the cap.  The kernel has one buffer, so a workgroup
+// waits for its own patch and the other workgroups of the CU are the overlap.
+constexpr int kStackAffinePatchCap = 32 * 1024;
+void stack_affine_tile(int idx, int* th, int* tw);
+int stack_affine_pick_tile(bool cubic, int oh, int ow);                  // a function of (output image shape, interpolation) only
+// rows: columns 0..3 of rows 1 and 2 of the caller's matrix (column 0 is not read)
+void stack_affine_fill_entry(const double rows[8], int plane, int cfg, bool cubic, int oh, int ow, bool force_direct, ExtractEntry* e);
+hipError_t launch_stack_affine(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
+                               const double* d_wts, int n, const AffineParams& p, int lds_bytes, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

@@ -257,6 +257,60 @@ def backproject_box_matrices(positions, angles, tilt_axis: int = 1, volume_shape
     return ms
 
 
+def _image_shape(shape, name: str) -> Tuple[int, int]:
+    """``(H, W)``, or ``(T, H, W)`` whose last two count: two positive ints, or ValueError."""
+    try:
+        s = tuple(shape)
+    except TypeError:
+        raise ValueError(f'{name} must be (H, W) or (T, H, W), positive ints')
+    if len(s) not in (2, 3) or not all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) and b > 0 for b in s):
+        raise ValueError(f'{name} must be (H, W) or (T, H, W), positive ints')
+    return int(s[-2]), int(s[-1])
+
+
+def stack_matrices(shifts=None, rotations=None, scales=None, image_shape=None, output_shape=None,
+                   rotation_units: str = 'deg') -> np.ndarray:
+    """Pull matrices (n, 3, 3), float64, on ``(h, w, 1)`` for ``StaticVolume.affine_stack``: image ``i`` appears in the output turned by
+    ``rotations[i]``, magnified by ``scales[i]`` about the centres and moved by ``shifts[i]``.
+
+    With ``ci = (image_shape - 1) / 2``, ``co = (output_shape - 1) / 2`` and ``R = [[cos t, -sin t], [sin t, cos t]]`` on ``(y, x)``, output
+    pixel ``p`` reads the image at ``q = ci + R^T . (p - co - shift_i) / s_i``.  ``shifts``: ``(n, 2)`` in pixels ``(y, x)``; ``rotations``:
+    ``(n,)``; ``scales``: ``(n,)``, non-zero; None = no shift, no turn, scale 1.  At least one of them must be given (it fixes ``n``).
+    ``image_shape`` (required) and ``output_shape`` (None = ``image_shape``): ``(H, W)``, or ``(T, H, W)`` whose last two count.
+    """
+    if rotation_units not in AVAILABLE_UNITS:
+        raise ValueError(f'rotation_units must be one of {AVAILABLE_UNITS}')
+    if image_shape is None:
+        raise ValueError('image_shape is required')
+    img = _image_shape(image_shape, 'image_shape')
+    out = img if output_shape is None else _image_shape(output_shape, 'output_shape')
+    given = [np.asarray(a, dtype=np.float64) for a in (shifts, rotations, scales) if a is not None]
+    if not given:
+        raise ValueError('one of shifts, rotations, scales must be given')
+    n = given[0].shape[0] if given[0].ndim else 0
+    sh = np.zeros((n, 2)) if shifts is None else np.asarray(shifts, dtype=np.float64)
+    th = np.zeros(n) if rotations is None else np.asarray(rotations, dtype=np.float64)
+    sc = np.ones(n) if scales is None else np.asarray(scales, dtype=np.float64)
+    if n == 0 or sh.shape != (n, 2) or th.shape != (n,) or sc.shape != (n,):
+        raise ValueError('shifts must have shape (n, 2), rotations and scales shape (n,), n > 0')
+    if not (np.isfinite(sh).all() and np.isfinite(th).all() and np.isfinite(sc).all()) or (sc == 0).any():
+        raise ValueError('shifts, rotations and scales must be finite, scales non-zero')
+    if rotation_units == 'deg':
+        th = np.deg2rad(th)
+    ci = (np.asarray(img, dtype=np.float64) - 1.0) / 2.0
+    co = (np.asarray(out, dtype=np.float64) - 1.0) / 2.0
+    c, s = np.cos(th), np.sin(th)
+    ms = np.zeros((n, 3, 3), dtype=np.float64)
+    # R^T / s
+    ms[:, 0, 0] = c / sc
+    ms[:, 0, 1] = s / sc
+    ms[:, 1, 0] = -s / sc
+    ms[:, 1, 1] = c / sc
+    ms[:, :2, 2] = ci - np.einsum('irc,ic->ir', ms[:, :2, :2], co + sh)
+    ms[:, 2, 2] = 1.0
+    return ms
+
+
 def _box_shape(box_shape) -> Tuple[int, int, int]:
     """Three positive ints, or ValueError."""
     try:

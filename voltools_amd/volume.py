@@ -15,7 +15,7 @@ from scipy.ndimage import affine_transform, map_coordinates, spline_filter
 from . import _native
 from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
 from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, place_matrices, tilt_matrices,
-                    backproject_matrices, backproject_box_matrices,
+                    backproject_matrices, backproject_box_matrices, stack_matrices,
                     get_available_devices, switch_to_device)
 from .utils.matrices import _box_shape
 
@@ -56,7 +56,7 @@ class StaticVolume:
         kernels that sample the plain layout; results are the same).  0 = no limit (or the ``VT_MAX_RESIDENT_GB`` environment default).
         The reference keeps one CUDA array per StaticVolume (``volume.py:37-45``).  ``stack`` (extension): the planes are independent
         images, a tilt series for ``backproject``; ``filt_*`` interpolations then prefilter inside each plane only (``spline_filter`` per
-        plane on ``device='cpu'``), and such a volume serves ``backproject`` / ``backproject_tilts`` alone.  With the other interpolations
+        plane on ``device='cpu'``), and such a volume serves the back-projections and ``affine_stack`` / ``align_stack`` alone.  With the other interpolations
         the flag changes nothing.  Not together with ``edge='scipy'``."""
         if data.ndim != 3:
             raise ValueError('Expected a 3D array')
@@ -1099,6 +1099,107 @@ class StaticVolume:
             raise ValueError('volume_shape and box_shape are required')
         ms = backproject_box_matrices(positions, angles, tilt_axis, volume_shape, box_shape, self.shape[1:], rotation_units, center)
         return self.backproject_boxes(ms, box_shape, weights, profile, output, accumulate=accumulate)
+
+    # -- per-image 2-D transforms of the stack: a stack in, a stack out (extension: tilt alignment, movie frames, regridding) ----
+    def affine_stack(self, matrices: np.ndarray, output_shape=None, weights=None, profile: bool = False, output=None, *,
+                     planes=None, _flags: int = 0) -> Union[np.ndarray, None]:
+        """This volume taken as a stack of ``T`` images ``(T, H, W)``, each resampled under its own 2-D affine map: ``out[i, h, w] =
+        float32(weights[i] * B_i[h, w])`` with ``B_i[h, w]`` image ``planes[i]`` interpolated in two dimensions at ``(y, x, 1) = M_i . (h,
+        w, 1)``, 0 outside the image -- ``backproject``'s definition for one entry and an output of depth 1, one image per entry instead of
+        their sum.  ``matrices``: ``(n, 3, 3)`` homogeneous pull matrices on ``(h, w, 1)`` (``utils.stack_matrices`` builds them from
+        shifts, rotations and scales), embedded into rows and columns 1, 2, 3 of a 4 x 4 matrix; or ``(n, 4, 4)`` as ``backproject`` takes
+        them, of which rows 1 and 2 and columns 1, 2, 3 count.  ``output_shape``: ``(Ho, Wo)``, None = ``(H, W)``.  The interpolation is the
+        volume's, in the plane: bilinear, or the 4 x 4 cubic B-spline; ``filt_*`` needs a volume built with ``stack=True``.
+        ``planes``: ``n`` image indices inside ``[0, T)``; None = ``0 .. n-1``, and then ``n`` must equal ``T``.  ``weights``: shape
+        ``(n,)``, converted to float64; None = ones.  Returns a float32 array ``(n, Ho, Wo)``, or fills ``output`` of that shape (numpy,
+        ``vt.empty`` device array, torch-ROCm tensor) and returns None on a GPU device, like ``backproject``.  An image does not depend on
+        the rest of the batch, and repeated calls give identical bits.  float64 matrices keep their precision; anything else is taken as
+        float32."""
+        ms = np.asarray(matrices)
+        if ms.ndim != 3 or ms.shape[1:] not in ((3, 3), (4, 4)) or ms.shape[0] == 0:
+            raise ValueError('matrices must have shape (n, 3, 3) or (n, 4, 4)')
+        dtype = np.float64 if ms.dtype == np.float64 else np.float32
+        if ms.shape[1:] == (3, 3):
+            m4 = np.zeros((ms.shape[0], 4, 4), dtype=dtype)
+            m4[:, 0, 0] = 1
+            m4[:, 1:, 1:] = ms
+            ms = m4
+        ms = np.ascontiguousarray(ms, dtype=dtype)
+        n = ms.shape[0]
+        try:
+            hw = tuple(self.shape[1:]) if output_shape is None else tuple(output_shape)
+        except TypeError:
+            raise ValueError('output_shape must be two positive ints')
+        if len(hw) != 2 or not all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) and b > 0 for b in hw):
+            raise ValueError('output_shape must be two positive ints')
+        shape = (n, int(hw[0]), int(hw[1]))
+        w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f'weights must have shape ({n},)')
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        if planes is None:
+            if n != self.shape[0]:
+                raise ValueError(f'{n} matrices for a stack of {self.shape[0]} images: planes must be given')
+            pl = None
+        else:
+            pl = np.asarray(planes)
+            if pl.shape != (n,) or not np.issubdtype(pl.dtype, np.integer):
+                raise ValueError(f'planes must be {n} integers')
+            if pl.min() < 0 or pl.max() >= self.shape[0]:
+                raise ValueError(f'planes must lie inside [0, {self.shape[0]})')
+            pl = np.ascontiguousarray(pl, dtype=np.int32)
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.interpolation.startswith('filt_') and not self.stack:
+            raise ValueError('affine_stack with a filt_* interpolation needs in-plane coefficients: build the volume with stack=True')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            res = np.empty(shape, dtype=np.float32)
+            h, x = np.meshgrid(*(np.arange(s, dtype=np.float64) for s in shape[1:]), indexing='ij')
+            coeffs = {}
+            t_start = time.time()
+            for i in range(n):
+                k = i if pl is None else int(pl[i])
+                if k not in coeffs:     # spline_filter per plane: the planes are independent images
+                    img = np.asarray(self.data[k], dtype=np.float64)
+                    coeffs[k] = spline_filter(img, order, output=np.float64, mode='constant') if prefilter else img
+                m = ms[i].astype(np.float64)
+                yy = m[1, 1] * h + m[1, 2] * x + m[1, 3]
+                xx = m[2, 1] * h + m[2, 2] * x + m[2, 3]
+                one = map_coordinates(coeffs[k], [yy, xx], order=order, mode='constant', cval=0.0, prefilter=False, output=np.float64)
+                res[i] = (0.0 + w[i] * one.astype(np.float32).astype(np.float64)).astype(np.float32)
+            if profile:
+                print(f'{n} images resampled in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        pl_ptr = None if pl is None else pl.ctypes.data
+        fn = self._lib.vt_volume_affine_stack_f64 if ms.dtype == np.float64 else self._lib.vt_volume_affine_stack
+        _native.check(fn(self._handle, n, ms.ctypes.data, pl_ptr, w.ctypes.data, shape[1], shape[2], ptr, flags), 'vt_volume_affine_stack')
+        if profile:
+            print(f'{n} images resampled in {self.timer_stop():.3f}ms')
+        return result
+
+    def align_stack(self, shifts=None, rotations=None, scales=None, output_shape=None, rotation_units: str = 'deg', weights=None,
+                    profile: bool = False, output=None, *, planes=None) -> Union[np.ndarray, None]:
+        """``affine_stack`` with the matrices of ``utils.stack_matrices`` for this stack's image shape: image ``planes[i]`` (None: ``i``)
+        appears in output image ``i`` turned by ``rotations[i]``, magnified by ``scales[i]`` about the centres and moved by
+        ``shifts[i]`` pixels ``(y, x)``; float64 matrices."""
+        ms = stack_matrices(shifts, rotations, scales, self.shape[1:], output_shape, rotation_units)
+        return self.affine_stack(ms, output_shape, weights, profile, output, planes=planes)
 
     def translate(self, translation: Vec3, profile: bool = False, output=None):
         return self.affine(translation_matrix(translation), profile, output)
