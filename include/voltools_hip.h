@@ -83,7 +83,7 @@ enum vt_create_flags {
                                 range with vt_volume_upload_planes and becomes usable with vt_volume_finalize              */
     VT_STACK = 32            /* the planes are independent images (a tilt series) for vt_volume_backproject: filt_* interpolations prefilter
                                 along axes 2 and 1 only, and such a handle (in-plane coefficients) refuses every sampling entry
-                                point but the back-projections and vt_volume_affine_stack with VT_EUNSUPPORTED.  With the other interpolations the flag changes nothing.  Not together with
+                                point but the back-projections, vt_volume_affine_stack and vt_volume_warp_stack with VT_EUNSUPPORTED.  With the other interpolations the flag changes nothing.  Not together with
                                 VT_EDGE_SCIPY, a slab window or VT_SRC_DEFERRED (VT_EUNSUPPORTED).                          */
 };
 
@@ -102,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -474,6 +474,51 @@ int vt_volume_warp(vt_volume_t* vol, const float* m4x4 /* or NULL = identity */,
                    int grid_d, int grid_h, int grid_w, int out_d, int out_h, int out_w, float* out, int flags);
 int vt_volume_warp_f64(vt_volume_t* vol, const double* m4x4 /* or NULL = identity */, const float* grid /* grid_d x grid_h x grid_w x 3 */,
                        int grid_d, int grid_h, int grid_w, int out_d, int out_h, int out_w, float* out, int flags);
+
+/* ---- warp_stack: every image of a resident stack resampled through its own 2-D displacement grid -- local, patch-based motion correction
+ * of movie frames, per-tilt beam-induced deformation, a lens or detector distortion shared by every image.  This is vt_volume_warp's grid
+ * rule on axes 1 and 2 added to vt_volume_affine_stack's pixel.  The handle holds T images of H x W as for vt_volume_affine_stack; m4x4s,
+ * planes, weights and out are that call's (m4x4s == NULL: the identity for every entry).  grids: host memory, n_grids x grid_h x grid_w x 2
+ * float32 in C order, n_grids == 1 (one grid shared by every entry) or n_grids == n; component 0 of a node moves y, component 1 moves x,
+ * in source pixels.  The nodes span the output image corner to corner; per axis either g_k == 1 or 2 <= g_k <= o_k, and a grid of the
+ * output's shape is a dense field.  For output pixel (h, w) of output image i, in float64:
+ *     a_y = fma(M_i[1,1], h, fma(M_i[1,2], w, M_i[1,3])),  a_x likewise with row 2
+ *     per in-plane axis k in {1, 2}:  r_k = (g_k - 1) / (o_k - 1)  (one float64 division on the host; 0 where g_k == 1)
+ *                                     q_k = v_k * r_k  (a rounded value of its own),  c_k = min(floor(q_k), g_k - 2),  f_k = q_k - c_k
+ *     u(h, w) = bilinear interpolation of grid G_i widened to float64: lerp(f, a, b) = fma(f, b - a, a) along axis 2, then axis 1; where
+ *               g_k == 1 the node itself
+ *     y = a_y + u_y,  x = a_x + u_x
+ *     out[i, h, w] = float32(weighted_add(+0.0, w_i, B))   if -0.5 <= y < H - 0.5 and -0.5 <= x < W - 0.5, else +0
+ * with B vt_volume_affine_stack's: the handle's interpolation taken in two dimensions in image planes[i] at ((int)floor(y), (float)(y -
+ * floor(y))), the same for x.
+ * Image i is a fixed expression of (M_i, G_i, planes[i], w_i, source, (out_h, out_w), interpolation, route): it does not depend on n, on its
+ * neighbours or its place in the batch, on whether its grid arrived as the shared grid or as its own copy, on host versus device output
+ * or on earlier calls.  An all-zero grid gives vt_volume_affine_stack's bits on the same route.  A linear handle writes the same bits on
+ * both routes; the cubic kinds agree to rounding.
+ * ONE workgroup per (entry, 2-D output tile) (last_kernel 22, last_grid = n x tiles entry-major, last_tile = (1, TH, TW) of
+ * vt_volume_affine_stack) loads the nodes its pixels touch into LDS -- at most (TH + 1)(TW + 1) -- and bounds its source patch by their
+ * range.  A tile stages its patch iff its entry's affine extents are below 4096 and its chain terms below 2^24 over the output, the
+ * tile's displacements are within 2^20 / (max(grid_h, grid_w) - 1) pixels, and its own patch (the affine patch with each extent grown by
+ * the range of the tile's nodes) fits 32 KiB; the other tiles gather from global memory inside the same launch.  VT_FORCE_DIRECT makes
+ * every tile gather, VT_FORCE_TILED selects the default; every other flag but VT_OUT_DEVICE is ignored.  The launch is sized without
+ * visiting tiles: the node block is (largest node count over the tile rows) x (largest over the tile columns) x 8 bytes rounded up to 16,
+ * the patch allocation is the largest over the entries that may stage of the patch formula with the range of the entry's WHOLE grid, and
+ * the 32 KiB cap itself (reported as 64 x 128) as soon as one of those bounds exceeds it.  last_lds_bytes = 128 + node block + allocation;
+ * last_lds_dims = (1, Ly, Lx) of the allocation, (0, 0, 0) when no entry may stage.  Tables and grids are uploaded per call, in one copy,
+ * into a buffer the handle recycles (n x 200 bytes + 8 bytes per node).
+ * Bounds (VT_EUNSUPPORTED beyond, decided before any array is read): n_grids x nodes x 2 < 2^31, n x tiles < 2^31, an image as for
+ * vt_volume_backproject, n x image bytes within size_t.  Handle kinds, filt_* without VT_STACK and VT_EDGE_SCIPY handles, n, dims, planes,
+ * non-finite matrices or weights: as vt_volume_affine_stack.  n_grids not 1 or n, grid dims outside the rule above, a non-finite node,
+ * NULL vol / grids / out: VT_EINVAL.  Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  A
+ * refusal leaves the handle usable. */
+int vt_volume_warp_stack(vt_volume_t* vol, int n, const float* m4x4s /* n x 16, or NULL = identity for every entry */,
+                         const float* grids /* n_grids x grid_h x grid_w x 2 */, int n_grids /* 1 = shared by all entries, or n */,
+                         int grid_h, int grid_w, const int32_t* planes /* n, or NULL */, const double* weights /* n, or NULL */,
+                         int out_h, int out_w, float* out, int flags);
+int vt_volume_warp_stack_f64(vt_volume_t* vol, int n, const double* m4x4s /* n x 16, or NULL = identity for every entry */,
+                             const float* grids /* n_grids x grid_h x grid_w x 2 */, int n_grids /* 1 = shared by all entries, or n */,
+                             int grid_h, int grid_w, const int32_t* planes /* n, or NULL */, const double* weights /* n, or NULL */,
+                             int out_h, int out_w, float* out, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

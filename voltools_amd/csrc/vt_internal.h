@@ -395,6 +395,34 @@ void stack_affine_fill_entry(const double rows[8], int plane, int cfg, bool cubi
 hipError_t launch_stack_affine(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
                                const double* d_wts, int n, const AffineParams& p, int lds_bytes, hipStream_t stream);
 
+// every image of the stack through its own 2-D displacement grid (vt_kernels_warpstack.hip, kind 22): kind 21's workgroups, tile and
+// entries plus kind 20's grid rule on axes 1 and 2.  A workgroup loads the nodes its tile touches into LDS (behind kWarpScratchFloats),
+// bounds its patch by their range and stages it, or gathers from global memory when the entry's flag is off, the hull is not granted
+// (kWarpHullLimit) or its own patch exceeds kStackAffinePatchCap.
+struct WarpStackHeader {
+    double r[2];               // (g_k - 1) / (o_k - 1) on axes 1 and 2; 0 where g_k == 1
+    int32_t g[2];              // nodes per axis
+    int32_t n_grids;           // 1: one grid shared by every entry, else one per entry
+    int32_t gm1_max;           // max(g) - 1
+    int32_t node_floats;       // floats of LDS between the scratch and the patch (the largest node block, a multiple of 4)
+    int32_t pad_[3];
+};
+static_assert(sizeof(WarpStackHeader) == 48, "the grids follow the header 16-byte aligned");
+// what last_lds_dims reports when an entry's bound exceeds the cap and the allocation is the cap itself: 64 x 128 floats
+constexpr int kWarpStackCapLy = 64, kWarpStackCapLx = 128;
+static_assert(kWarpStackCapLy * kWarpStackCapLx * 4 == kStackAffinePatchCap, "the cap as a patch");
+// the entry's flag (ExtractEntry::tiled) says only that its tiles MAY stage; rows as for stack_affine_fill_entry
+void warp_stack_fill_entry(const double rows[8], int plane, int cfg, bool cubic, int oh, int ow, bool force_direct, ExtractEntry* e);
+// folds the range of `nodes` nodes into r = (min y, max y, min x, max x); false: a component is not finite
+bool warp_stack_grid_range(const float* q, size_t nodes, float r[4]);
+// fills *hd and sizes the patch allocation from the grids' ranges (four floats per grid): L_alloc = (Ly, Lx), (0, 0) when no entry
+// carries the flag
+void warp_stack_plan(const ExtractEntry* e, int n, const float* ranges, int n_grids, const int g[2], int cfg, bool cubic, int oh, int ow,
+                     WarpStackHeader* hd, int L_alloc[2], int* patch_bytes);
+hipError_t launch_warp_stack(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
+                             const double* d_wts, const WarpStackHeader* d_hdr, const float* d_grids, int n, const AffineParams& p,
+                             int lds_bytes, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

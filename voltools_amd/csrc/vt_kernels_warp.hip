@@ -38,10 +38,11 @@
 // -- for a dense 512^3 grid: displacements above 2051 voxels -- the tile is neither classified nor staged: it takes the global-memory
 // route, where every voxel is tested and every tap is bounds-checked.
 //
-// The host sizes the launch from the same two functions (warp_cells, warp_tile_box), which hold float64 additions, one multiplication
-// followed by floor, and comparisons only -- nothing a compiler may contract -- so host and device agree on every tile's dims to the bit.
+// The host sizes the launch from the same two functions (warp_cells of vt_warp_common.h, warp_tile_box), which hold float64 additions,
+// one multiplication followed by floor, and comparisons only -- nothing a compiler may contract -- so host and device agree on every tile's dims to the bit.
 // The rule depends on (M, G, shapes, interpolation) only; the source's valid interval decides what is SKIPPED, never what is sized.
 #include "vt_box_common.h"
+#include "vt_warp_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -49,25 +50,6 @@
 #include <vector>
 
 namespace vt {
-
-// c_lo = cell of voxel `first`, n = nodes from there to the upper node of the cell of voxel `last` (first <= last).  r >= 0: monotone.
-__host__ __device__ __forceinline__ void warp_cells(int first, int last, double r, int g, int& c_lo, int& n)
-{
-    if (g == 1) { c_lo = 0; n = 1; return; }
-    const int a = (int)floor((double)first * r), b = (int)floor((double)last * r);
-    c_lo = a < g - 2 ? a : g - 2;
-    const int c_hi = b < g - 2 ? b : g - 2;
-    n = c_hi - c_lo + 2;
-}
-
-// Whether a tile may bound its source box by the hull of its nodes (the header's bound): U (max_k g_k - 1) <= kWarpHullLimit.
-__host__ __device__ __forceinline__ bool warp_hull_granted(const float (&umin)[3], const float (&umax)[3], int gm1_max)
-{
-    float U = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) U = fmaxf(U, fmaxf(fabsf(umin[r]), fabsf(umax[r])));
-    return (double)U * (double)gm1_max <= kWarpHullLimit;                    // (a 24-bit by 31-bit product: exact)
-}
 
 // The staged box of a tile whose nodes span [umin, umax] per component: extract_box_dims' formula on the affine extent plus umax - umin.
 // False: the tile gathers from global memory (hull bound not granted, extent absurd, or box beyond the cap).
@@ -96,15 +78,6 @@ __device__ __forceinline__ void warp_plane(const float* __restrict__ q, int su1,
         const double x1 = fma(f2, a11 - a10, a10);
         y[c] = fma(f1, x1 - x0, x0);
     }
-}
-
-// cell and fraction of output index x on an axis: q = x r is a value of its own (no fma may absorb it into q - c)
-__device__ __forceinline__ void warp_split(int x, double r, int gm2, int& c, double& f)
-{
-    const double q = rounded((double)x * r);
-    const int fl = (int)floor(q);
-    c = fl < gm2 ? fl : gm2;
-    f = q - (double)c;
 }
 
 template <int KIND, int TD, int TH, int TW>

@@ -346,3 +346,18 @@ def grid_nodes(grid_shape, output_shape) -> np.ndarray:
     nodes[..., 1] = axes[1][None, :, None]
     nodes[..., 2] = axes[2][None, None, :]
     return nodes
+
+
+def stack_grid_nodes(grid_shape, output_shape) -> np.ndarray:
+    """Output coordinates of the nodes of a 2-D displacement grid (``StaticVolume.warp_stack``): a float64 array ``(gH, gW, 2)`` whose
+    entry ``[j, k]`` is ``(j (Ho - 1) / (gH - 1), k (Wo - 1) / (gW - 1))`` -- the nodes span the output image corner to corner.  The 2-D
+    ``grid_nodes``, with its convention for an axis of one node: the middle of the output, ``(o - 1) / 2``.  Per axis either ``g == 1`` or
+    ``2 <= g <= o``.
+    """
+    try:
+        g, o = tuple(grid_shape), tuple(output_shape)
+    except TypeError:
+        raise ValueError('grid_shape and output_shape must be two positive ints each')
+    if len(g) != 2 or len(o) != 2:
+        raise ValueError('grid_shape and output_shape must be two positive ints each')
+    return grid_nodes((1,) + g, (1,) + o)[0, :, :, 1:]

@@ -44,6 +44,27 @@ def _warp_coordinates(disp: np.ndarray, m: np.ndarray, shape) -> np.ndarray:
     return coords
 
 
+def _warp_stack_coordinates(disp: np.ndarray, m: np.ndarray, shape):
+    """Source coordinates ``(y, x)``, float64 ``(Ho, Wo)`` each, of one entry of ``StaticVolume.warp_stack``: rows 1 and 2 of ``M`` on
+    ``(h, w, 1)`` plus the bilinear interpolation of the float32 grid ``disp`` ``(gH, gW, 2)`` -- ``_warp_coordinates`` in two dimensions,
+    lerps along axis 1 of the grid (x), then axis 0 (y)."""
+    u = disp.astype(np.float64)
+    for axis in (1, 0):
+        g, o = u.shape[axis], shape[axis]
+        if g == 1:
+            u = np.repeat(u, o, axis=axis) if o > 1 else u
+            continue
+        q = np.arange(o, dtype=np.float64) * ((g - 1) / (o - 1))
+        c = np.minimum(np.floor(q).astype(np.int64), g - 2)
+        f = (q - c).reshape([-1 if k == axis else 1 for k in range(3)])
+        a, b = np.take(u, c, axis=axis), np.take(u, c + 1, axis=axis)
+        u = a + f * (b - a)
+    h, w = (np.arange(n, dtype=np.float64) for n in shape)
+    yy = (m[1, 1] * h[:, None] + (m[1, 2] * w[None, :] + m[1, 3])) + u[..., 0]
+    xx = (m[2, 1] * h[:, None] + (m[2, 2] * w[None, :] + m[2, 3])) + u[..., 1]
+    return yy, xx
+
+
 class StaticVolume:
     """For StaticVolume transforms the boolean reshape cannot be given as an argument."""
 
@@ -56,7 +77,7 @@ class StaticVolume:
         kernels that sample the plain layout; results are the same).  0 = no limit (or the ``VT_MAX_RESIDENT_GB`` environment default).
         The reference keeps one CUDA array per StaticVolume (``volume.py:37-45``).  ``stack`` (extension): the planes are independent
         images, a tilt series for ``backproject``; ``filt_*`` interpolations then prefilter inside each plane only (``spline_filter`` per
-        plane on ``device='cpu'``), and such a volume serves the back-projections and ``affine_stack`` / ``align_stack`` alone.  With the other interpolations
+        plane on ``device='cpu'``), and such a volume serves the back-projections, ``affine_stack`` / ``align_stack`` and ``warp_stack`` alone.  With the other interpolations
         the flag changes nothing.  Not together with ``edge='scipy'``."""
         if data.ndim != 3:
             raise ValueError('Expected a 3D array')
@@ -1200,6 +1221,112 @@ class StaticVolume:
         ``shifts[i]`` pixels ``(y, x)``; float64 matrices."""
         ms = stack_matrices(shifts, rotations, scales, self.shape[1:], output_shape, rotation_units)
         return self.affine_stack(ms, output_shape, weights, profile, output, planes=planes)
+
+    def warp_stack(self, displacements, matrices=None, output_shape=None, weights=None, profile: bool = False, output=None, *,
+                   planes=None, _flags: int = 0) -> Union[np.ndarray, None]:
+        """``affine_stack`` with a 2-D displacement field per image: ``out[i, h, w] = float32(weights[i] * B_i[h, w])`` with ``B_i[h, w]``
+        image ``planes[i]`` interpolated in two dimensions at ``(y, x) = M_i . (h, w, 1) + u_i(h, w)``, 0 outside the image.
+        ``displacements``: control grids ``(n, gH, gW, 2)``, or ``(gH, gW, 2)`` for one grid shared by every entry, taken as float32;
+        component 0 moves ``y``, component 1 moves ``x``, in source pixels.  The nodes span the output image corner to corner
+        (``utils.stack_grid_nodes``), ``u_i`` is their bilinear interpolation in float64 -- ``warp``'s grid rule on axes 1 and 2.  Per axis
+        either one node or 2 up to the output size; a grid of the output's shape is a dense field.  ``matrices``: None for the identity,
+        or ``(n, 3, 3)`` / ``(n, 4, 4)`` as ``affine_stack`` takes them; float64 keeps its precision.  ``n`` is the number of matrices if
+        given, else the number of grids, else ``T``.  ``output_shape``, ``planes``, ``weights`` and ``output`` are ``affine_stack``'s.
+        Returns a float32 array ``(n, Ho, Wo)``, or fills ``output`` and returns None on a GPU device.  An image does not depend on the
+        rest of the batch.  ``device='cpu'`` evaluates the same float64 coordinates in numpy and hands them to
+        ``scipy.ndimage.map_coordinates`` per entry."""
+        disp = np.asarray(displacements)
+        if disp.ndim not in (3, 4) or disp.shape[-1] != 2 or 0 in disp.shape:
+            raise ValueError('displacements must have shape (n, gH, gW, 2) or (gH, gW, 2)')
+        shared = disp.ndim == 3
+        disp = np.ascontiguousarray(disp, dtype=np.float32)
+        if matrices is not None:
+            ms = np.asarray(matrices)
+            if ms.ndim != 3 or ms.shape[1:] not in ((3, 3), (4, 4)) or ms.shape[0] == 0:
+                raise ValueError('matrices must have shape (n, 3, 3) or (n, 4, 4)')
+            dtype = np.float64 if ms.dtype == np.float64 else np.float32
+            if ms.shape[1:] == (3, 3):
+                m4 = np.zeros((ms.shape[0], 4, 4), dtype=dtype)
+                m4[:, 0, 0] = 1
+                m4[:, 1:, 1:] = ms
+                ms = m4
+            ms = np.ascontiguousarray(ms, dtype=dtype)
+            n = ms.shape[0]
+        else:
+            ms = None
+            n = self.shape[0] if shared else disp.shape[0]
+        if not shared and disp.shape[0] != n:
+            raise ValueError(f'{disp.shape[0]} grids for {n} entries: one grid per entry, or one shared grid (gH, gW, 2)')
+        try:
+            hw = tuple(self.shape[1:]) if output_shape is None else tuple(output_shape)
+        except TypeError:
+            raise ValueError('output_shape must be two positive ints')
+        if len(hw) != 2 or not all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) and b > 0 for b in hw):
+            raise ValueError('output_shape must be two positive ints')
+        shape = (n, int(hw[0]), int(hw[1]))
+        gshape = disp.shape[-3:-1]
+        if not all(g == 1 or 2 <= g <= o for g, o in zip(gshape, shape[1:])):
+            raise ValueError(f'displacements of grid shape {gshape}: per axis 1 node, or 2 up to the output size {shape[1:]}')
+        if not np.isfinite(disp).all():
+            raise ValueError('displacements must be finite')
+        w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f'weights must have shape ({n},)')
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        if planes is None:
+            if n != self.shape[0]:
+                raise ValueError(f'{n} entries for a stack of {self.shape[0]} images: planes must be given')
+            pl = None
+        else:
+            pl = np.asarray(planes)
+            if pl.shape != (n,) or not np.issubdtype(pl.dtype, np.integer):
+                raise ValueError(f'planes must be {n} integers')
+            if pl.min() < 0 or pl.max() >= self.shape[0]:
+                raise ValueError(f'planes must lie inside [0, {self.shape[0]})')
+            pl = np.ascontiguousarray(pl, dtype=np.int32)
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.interpolation.startswith('filt_') and not self.stack:
+            raise ValueError('warp_stack with a filt_* interpolation needs in-plane coefficients: build the volume with stack=True')
+        if self.device == 'cpu':
+            order, prefilter = _scipy_arguments(self.interpolation)
+            res = np.empty(shape, dtype=np.float32)
+            coeffs = {}
+            t_start = time.time()
+            for i in range(n):
+                k = i if pl is None else int(pl[i])
+                if k not in coeffs:     # spline_filter per plane: the planes are independent images
+                    img = np.asarray(self.data[k], dtype=np.float64)
+                    coeffs[k] = spline_filter(img, order, output=np.float64, mode='constant') if prefilter else img
+                yy, xx = _warp_stack_coordinates(disp if shared else disp[i], np.eye(4) if ms is None else ms[i].astype(np.float64), shape[1:])
+                one = map_coordinates(coeffs[k], [yy, xx], order=order, mode='constant', cval=0.0, prefilter=False, output=np.float64)
+                res[i] = (0.0 + w[i] * one.astype(np.float32).astype(np.float64)).astype(np.float32)
+            if profile:
+                print(f'{n} images warped in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        pl_ptr = None if pl is None else pl.ctypes.data
+        m_ptr = None if ms is None else ms.ctypes.data
+        fn = self._lib.vt_volume_warp_stack_f64 if ms is not None and ms.dtype == np.float64 else self._lib.vt_volume_warp_stack
+        _native.check(fn(self._handle, n, m_ptr, disp.ctypes.data, 1 if shared else n, gshape[0], gshape[1], pl_ptr, w.ctypes.data,
+                         shape[1], shape[2], ptr, flags), 'vt_volume_warp_stack')
+        if profile:
+            print(f'{n} images warped in {self.timer_stop():.3f}ms')
+        return result
 
     def translate(self, translation: Vec3, profile: bool = False, output=None):
         return self.affine(translation_matrix(translation), profile, output)
