@@ -102,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack), 23 a 1-D filter along axis 1 or 2 of every image of a stack (one workgroup per (entry, strip of lines, segment of the filtered axis), float64 sums over the non-zero taps; vt_volume_filter_stack) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -519,6 +519,45 @@ int vt_volume_warp_stack_f64(vt_volume_t* vol, int n, const double* m4x4s /* n x
                              const float* grids /* n_grids x grid_h x grid_w x 2 */, int n_grids /* 1 = shared by all entries, or n */,
                              int grid_h, int grid_w, const int32_t* planes /* n, or NULL */, const double* weights /* n, or NULL */,
                              int out_h, int out_w, float* out, int flags);
+
+/* ---- filter_stack: every image of a resident stack convolved with a 1-D filter along axis 1 or 2 -- the ramp filter of weighted
+ * back-projection between alignment and reconstruction (after alignment the tilt axis lies along an array axis, and the filter runs along
+ * the other one), per-tilt low-pass, smoothing before cross-correlation, derivative taps.  The handle holds the stack (T, H, W) as for
+ * vt_volume_affine_stack; planes, weights and out are that call's, the output is n images of the source's own shape H x W.  taps: host
+ * memory, n_taps x k float64 in C order, n_taps == 1 (one row shared by every entry) or n_taps == n; k odd.  With L the extent of `axis`,
+ * r = (k - 1) / 2 and t the tap row of entry i, for output pixel (h, w) of image i with p = planes[i], axis 2:
+ *     acc = +0.0                                               float64
+ *     for j = 0 .. k-1 ascending, skipping every j with t[j] == 0 (either sign):
+ *         x = w + r - j
+ *         s = S[p, h, x] if 0 <= x < L;  pad 0: such a j is skipped like a zero tap;  pad 1: S[p, h, clamp(x, 0, L-1)]
+ *         acc = fma(t[j], (double)s, acc)
+ *     out[i, h, w] = float32(w_i * acc)
+ * and with axis 1 the same along h.  This is numpy.convolve(line, t, 'same'), scipy.ndimage.convolve1d(.., mode='constant' | 'nearest',
+ * origin=0).  Zero taps are skipped by definition: a non-finite sample spreads only through non-zero taps, and the even-offset zeros of
+ * a Ram-Lak row cost nothing.  An all-zero row writes +0.  (The kernel reads pad-0 samples outside the line as +0 instead of skipping
+ * them; the two differ only where acc is -0, which takes a product that underflows float64.)
+ * Image i is a fixed expression of (t, planes[i], w_i, source, axis, pad): it does not depend on n, on the other entries, on its place
+ * in the batch, on whether its row arrived as the shared row or as its own, on host versus device output or on earlier calls; zero taps
+ * added on both sides of a row change nothing, and filtering the transposed images along the other axis gives the transposed bits.
+ * ONE workgroup per (entry, strip of 64 lines across the unfiltered axis, segment of 64 outputs along the filtered axis) (last_kernel 23,
+ * last_grid = n x strips x segments entry-major, last_tile = (1, 64, 64) laid out (1, h, w)) walks the non-zero taps 128 consecutive j
+ * at a time and stages, per step, the 191 positions its outputs reach for its 64 lines in LDS, pad values included: last_lds_dims =
+ * (1, 191, 65), last_lds_bytes = 49660 whatever the image and k are.  A lane owns one line and 16 consecutive outputs as float64
+ * accumulators, and takes the taps 16 consecutive j at a time from a register window of 31 widened samples.  There is one route; every flag but VT_OUT_DEVICE is ignored.
+ * Device memory beyond the source: 32 bytes per entry, 16 bytes per non-zero tap and 8 (k + 128) bytes per tap row in a buffer the
+ * handle recycles.
+ * Bounds (VT_EUNSUPPORTED beyond, decided before any array is read): n_taps x k <= 2^26 (every odd k <= 2L - 1 is served up to there: no
+ * bound on k of its own), n x strips x segments < 2^31, n x image bytes within size_t, L <= 2^31 - 257.  The handle must hold samples: filt_*
+ * interpolations hold prefilter coefficients and are refused with VT_EUNSUPPORTED, VT_STACK or not (filter on a linear handle and build
+ * the filt_* handle from the result), as are VT_EDGE_SCIPY handles; VT_STACK is not required.  Slab handles and handles not yet
+ * finalized, n <= 0, k even, k < 1 or k > 2L - 1 (taps beyond reach nothing), n_taps not 1 or n, axis not 1 or 2, pad not 0 or 1,
+ * non-finite taps or weights, a plane index outside [0, T), planes == NULL with n != T, NULL vol / taps / out: VT_EINVAL.  Host `out`:
+ * returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  The handle's output shape is neither read nor
+ * changed.  A refusal leaves the handle usable. */
+int vt_volume_filter_stack(vt_volume_t* vol, int n, const int32_t* planes /* n, or NULL */,
+                           const double* taps /* n_taps x k, C order */, int n_taps /* 1 or n */, int k,
+                           int axis /* 1 or 2 */, int pad /* 0 zero, 1 edge */,
+                           const double* weights /* n, or NULL = all 1 */, float* out /* n x H x W */, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

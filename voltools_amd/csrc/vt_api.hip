@@ -2651,6 +2651,80 @@ int do_warp_stack(vt_volume* v, int n, const MT* m4x4s, const float* grids, int 
     return res.finish();
 }
 
+// n images of the stack's own shape, image i = image planes[i] convolved along `axis` (1 or 2) with tap row i (row 0 when n_taps == 1),
+// times weight i: numpy.convolve(line, taps, 'same') with zero (pad 0) or edge (pad 1) samples outside, summed in float64 over the
+// non-zero taps in ascending order, rounded once (vt_kernels_filterstack.hip has the expression).  One launch of kernel 23, n x strips x
+// segments workgroups.  The tables are n FilterEntry, every tap row compacted to the FilterTap pairs of its non-zero taps, and the rows
+// themselves, each followed by kFilterChunk zeros.  The handle must hold samples: filt_* handles hold coefficients.  Does not read or
+// change the handle's own output shape.
+int do_filter_stack(vt_volume* v, int n, const int32_t* planes, const double* taps, int n_taps, int k, int axis, int pad,
+                    const double* weights, float* out, int flags)
+{
+    if (!v || !taps || !out) return fail(VT_EINVAL, "NULL argument");
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_whole_volume(v, "filter_stack"))) return rc;
+    if (v->edge_pad) return fail(VT_EUNSUPPORTED, "filter_stack is not available on VT_EDGE_SCIPY handles");
+    if (is_filtered(v->interp))
+        return fail(VT_EUNSUPPORTED, "the handle holds prefilter coefficients, not samples: filter on a linear handle and build the filt_* "
+                                     "handle from the result");
+    if (axis != 1 && axis != 2) return fail(VT_EINVAL, "axis %d (1 or 2)", axis);
+    if (pad != 0 && pad != 1) return fail(VT_EINVAL, "pad %d (0 zero, 1 edge)", pad);
+    if (n_taps != 1 && n_taps != n) return fail(VT_EINVAL, "%d tap rows for %d images (1 or n)", n_taps, n);
+    const int L = axis == 2 ? v->W : v->H, lines = axis == 2 ? v->H : v->W;
+    if (k < 1 || !(k & 1) || (int64_t)k > 2 * (int64_t)L - 1)
+        return fail(VT_EINVAL, "%d taps: an odd count inside [1, %lld] for an extent of %d", k, 2 * (long long)L - 1, L);
+    // the bounds, before anything of the caller's arrays is read
+    const int64_t wgs = filter_stack_strips(lines) * filter_stack_segments(L);
+    if (wgs * n > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "grid too large (%d images x %lld workgroups)", n, (long long)wgs);
+    const size_t image = (size_t)v->H * v->W;
+    if (image > (SIZE_MAX / sizeof(float)) / (size_t)n) return fail(VT_EUNSUPPORTED, "output too large (%d images)", n);
+    if (L > kFilterStackMaxExtent) return fail(VT_EUNSUPPORTED, "an extent of %d along axis %d", L, axis);
+    if ((int64_t)n_taps * k > kFilterStackMaxTaps)
+        return fail(VT_EUNSUPPORTED, "%d rows of %d taps: more than %lld taps in one call", n_taps, k, (long long)kFilterStackMaxTaps);
+    if ((rc = select_device(v))) return rc;
+    const size_t all = (size_t)n_taps * (size_t)k;
+    size_t nnz_all = 0;
+    for (size_t i = 0; i < all; ++i) {
+        if (!std::isfinite(taps[i])) return fail(VT_EINVAL, "tap %zu of row %zu is not finite", i % (size_t)k, i / (size_t)k);
+        nnz_all += taps[i] != 0.0;
+    }
+    if ((rc = check_finite_weights(weights, (size_t)n)) || (rc = check_planes(v, n, planes, ""))) return rc;
+
+    constexpr size_t kFE = sizeof(FilterEntry) / sizeof(double);
+    const size_t taps_at = kFE * (size_t)n, rows_at = taps_at + 2 * nnz_all, row_len = (size_t)k + kFilterChunk;
+    if ((rc = begin_tables(v, rows_at + (size_t)n_taps * row_len))) return rc;
+    FilterEntry* const e = reinterpret_cast<FilterEntry*>(v->h_batch_m.data());
+    FilterTap* const tp = reinterpret_cast<FilterTap*>(v->h_batch_m.data() + taps_at);
+    double* const rows = v->h_batch_m.data() + rows_at;
+    size_t at = 0;
+    for (int row = 0; row < n_taps; ++row) {
+        const size_t first = at;
+        const double* t = taps + (size_t)row * (size_t)k;
+        double* const dense = rows + (size_t)row * row_len;
+        std::memcpy(dense, t, (size_t)k * sizeof(double));
+        std::fill(dense + k, dense + row_len, 0.0);
+        for (int j = 0; j < k; ++j)
+            if (t[j] != 0.0) { tp[at].t = t[j]; tp[at].j = j; tp[at].pad_ = 0; ++at; }
+        for (int i = row; i < (n_taps == 1 ? n : row + 1); ++i) {
+            e[i].weight = weights ? weights[i] : 1.0;
+            e[i].first = (int64_t)first;
+            e[i].dense = (int64_t)((size_t)row * row_len);
+            e[i].plane = planes ? planes[i] : i;
+            e[i].nnz = (int32_t)(at - first);
+        }
+    }
+    const int T[3] = {1, axis == 2 ? kFilterStrip : kFilterSeg, axis == 2 ? kFilterSeg : kFilterStrip};
+    const int Lds[3] = {1, kFilterSeg + kFilterChunk - 1, kFilterStrip + 1};
+    record_launch(v, 23, T, Lds, kFilterLdsBytes, wgs * n);
+
+    ResultScope res(v, out, image * (size_t)n * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open()) || (rc = upload_tables(v))) return rc;
+    VT_HIP(launch_filter_stack(v->d_src, res.ptr<float>(), reinterpret_cast<const FilterEntry*>(v->d_batch_m),
+                               reinterpret_cast<const FilterTap*>(v->d_batch_m + taps_at), v->d_batch_m + rows_at, n, v->H, v->W, v->P, axis, pad,
+                               k, v->stream));
+    return res.finish();
+}
+
 // a float32 batch of n matrices in float64
 std::vector<double> widened(const float* m4x4s, int n)
 {
@@ -3102,6 +3176,12 @@ int vt_volume_warp_stack_f64(vt_volume_t* v, int n, const double* m4x4s, const f
                              const int32_t* planes, const double* weights, int out_h, int out_w, float* out, int flags)
 {
     return do_warp_stack(v, n, m4x4s, grids, n_grids, grid_h, grid_w, planes, weights, out_h, out_w, out, flags);
+}
+
+int vt_volume_filter_stack(vt_volume_t* v, int n, const int32_t* planes, const double* taps, int n_taps, int k, int axis, int pad,
+                           const double* weights, float* out, int flags)
+{
+    return do_filter_stack(v, n, planes, taps, n_taps, k, axis, pad, weights, out, flags);
 }
 
 int vt_volume_extract_dot(vt_volume_t* v, int n, const float* m4x4s, const float* tmpl, const float* mask, int box_d, int box_h, int box_w,

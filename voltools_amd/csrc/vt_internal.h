@@ -423,6 +423,32 @@ hipError_t launch_warp_stack(int cfg, int interp, const float* src, float* out, 
                              const double* d_wts, const WarpStackHeader* d_hdr, const float* d_grids, int n, const AffineParams& p,
                              int lds_bytes, hipStream_t stream);
 
+// a 1-D filter along axis 1 or 2 of every image of the stack (vt_kernels_filterstack.hip, kind 23): one workgroup per (entry, strip of
+// kFilterStrip lines across the unfiltered axis, segment of kFilterSeg outputs along the filtered axis), grid = n x strips x segments
+// entry-major.  The taps are walked kFilterChunk consecutive j at a time; per chunk the workgroup stages kFilterSeg + kFilterChunk - 1
+// positions of its lines, (kFilterStrip + 1) floats apart.
+constexpr int kFilterStrip = 64, kFilterSeg = 64, kFilterChunk = 128;
+constexpr int64_t kFilterStackMaxTaps = (int64_t)1 << 26;    // n_taps x k of one call: at most 1.5 GiB of pairs and rows in the table buffer
+constexpr int kFilterStackMaxExtent = 0x7fffffff - 256;       // the kernel's staged positions, extent + block, are 32-bit
+constexpr int kFilterLdsBytes =(kFilterSeg + kFilterChunk - 1) * (kFilterStrip + 1) * 4;
+struct FilterEntry {
+    double weight;
+    int64_t first;             // index of the entry's first FilterTap
+    int64_t dense;             // index of tap 0 of the entry's row among the uploaded rows (k taps, then kFilterChunk zeros)
+    int32_t plane;
+    int32_t nnz;               // its non-zero taps
+};
+struct FilterTap {
+    double t;
+    int32_t j;                 // the tap's index in the caller's row, ascending within a row
+    int32_t pad_;
+};
+static_assert(sizeof(FilterEntry) == 32 && sizeof(FilterTap) == 16, "tables of whole doubles, a tap per 16-byte scalar load");
+inline int64_t filter_stack_strips(int lines) { return ((int64_t)lines + kFilterStrip - 1) / kFilterStrip; }
+inline int64_t filter_stack_segments(int L) { return ((int64_t)L + kFilterSeg - 1) / kFilterSeg; }
+hipError_t launch_filter_stack(const float* src, float* out, const FilterEntry* d_tab, const FilterTap* d_taps, const double* d_rows, int n,
+                               int H, int W, int P, int axis, int pad, int k, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

@@ -10,12 +10,12 @@ import time
 from typing import Tuple, Union
 
 import numpy as np
-from scipy.ndimage import affine_transform, map_coordinates, spline_filter
+from scipy.ndimage import affine_transform, convolve1d, map_coordinates, spline_filter
 
 from . import _native
 from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
 from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, place_matrices, tilt_matrices,
-                    backproject_matrices, backproject_box_matrices, stack_matrices,
+                    backproject_matrices, backproject_box_matrices, stack_matrices, ramp_taps,
                     get_available_devices, switch_to_device)
 from .utils.matrices import _box_shape
 
@@ -1327,6 +1327,106 @@ class StaticVolume:
         if profile:
             print(f'{n} images warped in {self.timer_stop():.3f}ms')
         return result
+
+    # -- a 1-D filter per image of the stack (extension: the ramp filter of weighted back-projection, low-pass, derivative taps) ----
+    def filter_stack(self, taps, axis: int = 2, weights=None, pad: str = 'zero', profile: bool = False, output=None, *,
+                     planes=None, _flags: int = 0) -> Union[np.ndarray, None]:
+        """This volume taken as a stack of ``T`` images ``(T, H, W)``, each convolved with a 1-D filter along ``axis`` (1 or 2):
+        ``out[i] = float32(weights[i] * convolve(image planes[i], taps_i))`` with ``numpy.convolve(line, taps_i, 'same')`` on every line
+        along ``axis``, which is ``scipy.ndimage.convolve1d(image, taps_i, axis, mode='constant' | 'nearest', origin=0)``.  ``taps``:
+        ``(K,)`` for one row shared by every entry or ``(n, K)`` for a row per entry, converted to float64; ``K`` odd and at most ``2 L
+        - 1`` for an axis of extent ``L``.  ``pad``: ``'zero'`` reads 0 outside the image, ``'edge'`` the nearest sample.  ``planes``:
+        ``n`` image indices inside ``[0, T)``; None = ``0 .. n-1``, and then ``n`` must equal ``T`` (``n`` is the number of tap rows if
+        there are several, else of planes, else ``T``).  ``weights``: shape ``(n,)``, float64; None = ones.  The volume must hold samples:
+        a ``filt_*`` interpolation holds prefilter coefficients and is refused -- filter on a ``'linear'`` volume and build the
+        ``filt_*`` one from the result.  ``stack=True`` is not needed.  Returns a float32 array ``(n, H, W)``, or fills ``output`` of
+        that shape (numpy, ``vt.empty`` device array, torch-ROCm tensor) and returns None on a GPU device, like ``affine_stack``.
+        On a GPU device the sum runs in float64 over the non-zero taps only, in ascending order, and is rounded once; an image does not
+        depend on the rest of the batch and repeated calls give identical bits.  ``device='cpu'`` is ``convolve1d`` on the float64 image,
+        times the weight, cast to float32: the two devices agree to rounding on finite data only, since a zero tap times a non-finite
+        sample is skipped on the GPU and NaN in scipy."""
+        t = np.asarray(taps, dtype=np.float64)
+        if t.ndim not in (1, 2) or 0 in t.shape:
+            raise ValueError('taps must have shape (K,) or (n, K)')
+        shared = t.ndim == 1
+        t = np.ascontiguousarray(t)
+        if axis not in (1, 2) or isinstance(axis, bool):
+            raise ValueError('axis must be 1 or 2')
+        if pad not in ('zero', 'edge'):
+            raise ValueError("pad must be 'zero' or 'edge'")
+        extent = self.shape[axis]
+        k = t.shape[-1]
+        if k % 2 == 0 or k > 2 * extent - 1:
+            raise ValueError(f'{k} taps: an odd count of at most {2 * extent - 1} for an axis of extent {extent}')
+        if not np.isfinite(t).all():
+            raise ValueError('taps must be finite')
+        if planes is None:
+            pl = None
+            n = self.shape[0] if shared else t.shape[0]
+            if n != self.shape[0]:
+                raise ValueError(f'{n} tap rows for a stack of {self.shape[0]} images: planes must be given')
+        else:
+            pl = np.asarray(planes)
+            if pl.ndim != 1 or pl.size == 0 or not np.issubdtype(pl.dtype, np.integer):
+                raise ValueError('planes must be a vector of integers')
+            n = pl.shape[0]
+            if pl.min() < 0 or pl.max() >= self.shape[0]:
+                raise ValueError(f'planes must lie inside [0, {self.shape[0]})')
+            pl = np.ascontiguousarray(pl, dtype=np.int32)
+        if not shared and t.shape[0] != n:
+            raise ValueError(f'{t.shape[0]} tap rows for {n} entries: one row per entry, or one shared row (K,)')
+        w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f'weights must have shape ({n},)')
+        if not np.isfinite(w).all():
+            raise ValueError('weights must be finite')
+        shape = (n, int(self.shape[1]), int(self.shape[2]))
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.interpolation.startswith('filt_'):
+            raise ValueError('filter_stack needs samples, and a filt_* volume holds prefilter coefficients: filter on a linear volume '
+                             'and build the filt_* volume from the result')
+        if self.device == 'cpu':
+            res = np.empty(shape, dtype=np.float32)
+            t_start = time.time()
+            for i in range(n):
+                img = np.asarray(self.data[i if pl is None else int(pl[i])], dtype=np.float64)
+                one = convolve1d(img, t if shared else t[i], axis=axis - 1, mode='constant' if pad == 'zero' else 'nearest', cval=0.0, origin=0)
+                res[i] = (w[i] * one).astype(np.float32)
+            if profile:
+                print(f'{n} images filtered in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = _native.host_result(shape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        pl_ptr = None if pl is None else pl.ctypes.data
+        _native.check(self._lib.vt_volume_filter_stack(self._handle, n, pl_ptr, t.ctypes.data, 1 if shared else n, k, axis,
+                                                       0 if pad == 'zero' else 1, w.ctypes.data, ptr, flags), 'vt_volume_filter_stack')
+        if profile:
+            print(f'{n} images filtered in {self.timer_stop():.3f}ms')
+        return result
+
+    def ramp_filter(self, tilt_axis: int = 1, window: str = 'ramp', half_width=None, weights=None, pad: str = 'edge',
+                    output=None) -> Union[np.ndarray, None]:
+        """The filter of weighted back-projection on a tilt series whose tilt axis lies along array axis ``tilt_axis`` of the volume it
+        came from (the convention of ``tilt_series`` and ``backproject_tilts``): ``filter_stack`` with ``utils.ramp_taps(L, window,
+        half_width)`` along the in-plane axis that is not the tilt axis, ``tilt_axis=1`` -> ``axis=2`` and ``tilt_axis=2`` -> ``axis=1``,
+        ``L`` that axis's extent."""
+        if tilt_axis not in (1, 2) or isinstance(tilt_axis, bool):
+            raise ValueError('tilt_axis must be 1 or 2')
+        axis = 3 - tilt_axis
+        return self.filter_stack(ramp_taps(self.shape[axis], window, half_width), axis, weights, pad, False, output)
 
     def translate(self, translation: Vec3, profile: bool = False, output=None):
         return self.affine(translation_matrix(translation), profile, output)
