@@ -102,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack), 23 a 1-D filter along axis 1 or 2 of every image of a stack (one workgroup per (entry, strip of lines, segment of the filtered axis), float64 sums over the non-zero taps; vt_volume_filter_stack) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack), 23 a 1-D filter along axis 1 or 2 of every image of a stack (one workgroup per (entry, strip of lines, segment of the filtered axis), float64 sums over the non-zero taps; vt_volume_filter_stack), 24 shift scores of every image of a stack against a reference per patch of a grid (one workgroup per (entry, patch, piece of 64 x 64 pixels, block of shifts), float64 sums, pieces added by a second launch; vt_volume_correlate_stack) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -558,6 +558,54 @@ int vt_volume_filter_stack(vt_volume_t* vol, int n, const int32_t* planes /* n, 
                            const double* taps /* n_taps x k, C order */, int n_taps /* 1 or n */, int k,
                            int axis /* 1 or 2 */, int pad /* 0 zero, 1 edge */,
                            const double* weights /* n, or NULL = all 1 */, float* out /* n x H x W */, int flags);
+
+/* ---- correlate_stack: the cross-correlation of every image of a resident stack, or of every patch of it, with a reference over a window
+ * of integer shifts -- the scores that coarse tilt alignment (every tilt against its neighbour), patch tracking and local motion
+ * correction (every patch against the frame sum) take their shifts from: the step that produces vt_volume_affine_stack's shifts and
+ * vt_volume_warp_stack's grids.  The handle holds samples S (T, H, W); the rules for the handle are vt_volume_filter_stack's.  Entry i
+ * pairs image p = planes[i] (NULL: image i, n = T) with a reference r_i (H, W), float32: host memory `refs`, n_refs x H x W in C order
+ * with n_refs == 1 (shared) or n, or, with refs == NULL, the resident image ref_planes[i] (nothing is uploaded: a tilt against its
+ * neighbour).  A patch grid (grid_h, grid_w), 1 <= grid_h <= H and 1 <= grid_w <= W, cuts the image into rectangles in integer
+ * arithmetic: patch (a, b) covers rows [a H / grid_h, (a+1) H / grid_h) and columns [b W / grid_w, (b+1) W / grid_w) by floor
+ * division.  The shift window is (r_h, r_w), 0 <= r_h <= H - 1 and 0 <= r_w <= W - 1 (shifts beyond overlap nothing).
+ *     out[i, a, b, u, v] = sum over (y, x) in patch (a, b) of  (double) r_i[y, x] * (double) s(y + u - r_h, x + v - r_w)
+ *     s(y', x') = S[p, y', x'] inside the image, +0 outside
+ * out: float64, n x grid_h x grid_w x (2 r_h + 1) x (2 r_w + 1) in C order, host memory or device memory with VT_OUT_DEVICE.  Every
+ * product is exact in float64 (both factors carry 24 bits); every addition is rounded, by fma.  Outside samples are +0 MULTIPLIED, not
+ * skipped: a non-finite reference pixel makes every score of its patch non-finite, a non-finite image pixel reaches exactly the
+ * (patch, shift) pairs whose window covers it.  Host refs with non-finite entries are refused (VT_EINVAL), like vt_volume_extract_dot's
+ * template; resident references are taken as they are.
+ * The order of additions is fixed by the patch's rows and columns alone.  A patch is cut from its own first row and column into pieces
+ * of 64 x 64 pixels, piece (py, px) row-major, and a piece into four bands of 16 rows.  A band sum starts from +0 and takes its
+ * pixels row by row, ascending x within a row, acc = fma(r, s, acc).  A piece sum is ((band 0 + band 1) + band 2) + band 3 (a band
+ * the piece does not reach is +0).  A score is the piece sums added in ascending piece index, starting from piece 0 itself, by a second
+ * small launch; no atomics, no memset.  A score is therefore a fixed expression of (r_i, image p, patch, shift, H, W): it does not
+ * depend on n, on the other entries or its place in the batch, on the other patches, on r_h and r_w beyond the shift lying inside the
+ * window, on whether the reference came shared, per entry or resident, on host versus device output, on earlier calls or on recycled
+ * memory; repeated calls give identical bits.
+ * ONE workgroup per (entry, patch, piece, block of shifts) (last_kernel 24, last_tile = (1, 64, 64): the piece).  A lane owns one
+ * shift row and a run of cv consecutive column shifts as float64 accumulators, cv = 11 if that pads 2 r_w + 1 to fewer columns than 9
+ * does, else 9; runs = min(7, ceil((2 r_w + 1) / cv)) runs lie side by side and rows_blk = min(64 / runs, 2 r_h + 1) shift rows on top of
+ * each other in a wave, so a block is rows_blk x runs cv shifts and a larger window goes onto the grid.  The workgroup stages the
+ * reference piece (16 KiB) and the 64 + rows_blk - 1 rows of 63 + runs cv image samples the block reaches, at a pitch of 64 + runs cv
+ * floats, zeros outside the image included: last_lds_dims = (1, 64 + rows_blk - 1, 64 + runs cv), last_lds_bytes = 16384 + 4 x rows x
+ * pitch, at most 56992.  Every patch gets the piece grid of the call's largest patch (a piece past a smaller patch's end adds +0);
+ * last_grid = the workgroups of the call's last launch, (entries x patches of it) x pieces x blocks.  A call whose partial sums (pieces
+ * x shifts x 8 bytes per (entry, patch) when a patch has several pieces) would exceed 64 MiB is split into launches inside the call.
+ * Every flag but VT_OUT_DEVICE is ignored.  Device memory beyond the source: 8 bytes per entry and the host references, in the table
+ * buffer, and the partial sums, in a buffer the handle recycles.
+ * Bounds (VT_EUNSUPPORTED beyond, decided before any array is read): n x grid_h x grid_w x (2 r_h + 1) x (2 r_w + 1) < 2^31 output
+ * elements; pieces x blocks of one patch < 2^31 workgroups and pieces x shifts of one patch < 2^31 partial sums (more workgroups than
+ * that in a call are split into launches); n_refs x H x W <= 2^30 host reference pixels.  filt_* handles hold prefilter coefficients
+ * and are refused with VT_EUNSUPPORTED, as are VT_EDGE_SCIPY handles; VT_STACK is not required.  Slab handles and handles not yet
+ * finalized, n <= 0, n_refs not 0, 1 or n (0 only with ref_planes, which ignores it), refs and ref_planes both NULL or both given, a
+ * plane or reference plane outside [0, T), planes == NULL with n != T, a grid or window outside the ranges above, NULL vol / out:
+ * VT_EINVAL.  Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  The handle's output shape
+ * is neither read nor changed.  A refusal leaves the handle usable. */
+int vt_volume_correlate_stack(vt_volume_t* vol, int n, const int32_t* planes /* n, or NULL */,
+                              const float* refs /* n_refs x H x W, or NULL */, int n_refs /* 1 or n; 0 with ref_planes */,
+                              const int32_t* ref_planes /* n, or NULL */, int grid_h, int grid_w, int r_h, int r_w,
+                              double* out /* n x grid_h x grid_w x (2 r_h + 1) x (2 r_w + 1) */, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

@@ -2725,6 +2725,82 @@ int do_filter_stack(vt_volume* v, int n, const int32_t* planes, const double* ta
     return res.finish();
 }
 
+// n x gh x gw x (2 rh + 1) x (2 rw + 1) float64: for entry i, patch (a, b) of the grid and shift (u, v), the sum over the patch of
+// reference i times image planes[i] displaced by (u - rh, v - rw), zeros outside the image (vt_kernels_correlatestack.hip has the
+// expression and the order of additions).  The reference of entry i is host image i of `refs` (image 0 when n_refs == 1) or, with refs
+// == NULL, the resident image ref_planes[i].  Launches of kernel 24 over runs of (entry, patch) units whose partials stay within the
+// cap, each followed by its reduction when a patch has several pieces.  Does not read or change the handle's own output shape.
+int do_correlate_stack(vt_volume* v, int n, const int32_t* planes, const float* refs, int n_refs, const int32_t* ref_planes, int gh, int gw,
+                       int rh, int rw, double* out, int flags)
+{
+    if (!v || !out) return fail(VT_EINVAL, "NULL argument");
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_whole_volume(v, "correlate_stack"))) return rc;
+    if (v->edge_pad) return fail(VT_EUNSUPPORTED, "correlate_stack is not available on VT_EDGE_SCIPY handles");
+    if (is_filtered(v->interp))
+        return fail(VT_EUNSUPPORTED, "the handle holds prefilter coefficients, not samples: correlate on a linear handle");
+    if (n_refs != 0 && n_refs != 1 && n_refs != n) return fail(VT_EINVAL, "%d references for %d entries (1 or n)", n_refs, n);
+    if ((refs != nullptr) == (ref_planes != nullptr)) return fail(VT_EINVAL, "exactly one of refs and ref_planes must be given");
+    if (refs && n_refs == 0) return fail(VT_EINVAL, "0 host references");
+    if (gh < 1 || gh > v->H || gw < 1 || gw > v->W) return fail(VT_EINVAL, "patch grid (%d,%d) for images of (%d,%d)", gh, gw, v->H, v->W);
+    if (rh < 0 || rh > v->H - 1 || rw < 0 || rw > v->W - 1)
+        return fail(VT_EINVAL, "shift window (%d,%d) for images of (%d,%d): at most (%d,%d)", rh, rw, v->H, v->W, v->H - 1, v->W - 1);
+    // the bounds, before anything of the caller's arrays is read
+    if (rh >= (1 << 30) || rw >= (1 << 30)) return fail(VT_EUNSUPPORTED, "output too large (a window of (%d,%d))", rh, rw);
+    const CorrPlan cp = correlate_stack_plan(v->H, v->W, gh, gw, rh, rw);
+    const int64_t nunv = (int64_t)cp.nu * cp.nv;                       // < 2^62
+    const int64_t per = (int64_t)gh * gw;                              // patches per entry
+    if (nunv > 0x7fffffffLL || per > 0x7fffffffLL || per * nunv > 0x7fffffffLL || per * nunv * n > 0x7fffffffLL)
+        return fail(VT_EUNSUPPORTED, "output too large (%d entries x %lld patches x %lld shifts)", n, (long long)per, (long long)nunv);
+    if (cp.unit_wgs > 0x7fffffffLL || cp.unit_part > 0x7fffffffLL)
+        return fail(VT_EUNSUPPORTED, "%lld workgroups and %lld partial sums per patch", (long long)cp.unit_wgs, (long long)cp.unit_part);
+    const size_t image = (size_t)v->H * v->W;
+    if (refs && image * (size_t)n_refs > ((size_t)1 << 30)) return fail(VT_EUNSUPPORTED, "%d host references: more than 2^30 pixels", n_refs);
+    if ((rc = select_device(v)) || (rc = check_planes(v, n, planes, ""))) return rc;
+    if (ref_planes) {
+        for (int i = 0; i < n; ++i)
+            if (ref_planes[i] < 0 || ref_planes[i] >= v->D)
+                return fail(VT_EINVAL, "reference plane index %d of entry %d outside [0, %d)", ref_planes[i], i, v->D);
+    } else {
+        for (size_t i = 0; i < image * (size_t)n_refs; ++i)
+            if (!std::isfinite(refs[i])) return fail(VT_EINVAL, "pixel %zu of reference %zu is not finite", i % image, i / image);
+    }
+
+    // the call's tables in one staging vector: one CorrEntry per entry, then the host references as they came
+    const size_t refs_at = (size_t)n, ref_dbl = refs ? (image * (size_t)n_refs + 1) / 2 : 0;
+    if ((rc = begin_tables(v, refs_at + ref_dbl))) return rc;
+    CorrEntry* const e = reinterpret_cast<CorrEntry*>(v->h_batch_m.data());
+    for (int i = 0; i < n; ++i) {
+        e[i].plane = planes ? planes[i] : i;
+        e[i].ref = ref_planes ? ref_planes[i] : (n_refs == 1 ? 0 : i);
+    }
+    if (refs) std::memcpy(v->h_batch_m.data() + refs_at, refs, image * (size_t)n_refs * sizeof(float));
+
+    // units per launch: their partials stay within the cap (one unit's partials at least), the grid within 2^31
+    const int64_t units = per * n;
+    int64_t per_launch = std::min<int64_t>(units, 0x7fffffffLL / cp.unit_wgs);
+    if (cp.unit_part > 0)
+        per_launch = std::min<int64_t>(per_launch, std::max<int64_t>(1, v->tune.dot_part_cap / (cp.unit_part * (int64_t)sizeof(double))));
+    if (cp.unit_part > 0 && (rc = ensure_partials(v, (size_t)per_launch * (size_t)cp.unit_part * sizeof(double)))) return rc;
+    if ((rc = upload_tables(v))) return rc;
+    ResultScope res(v, out, (size_t)(units * nunv) * sizeof(double), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open())) return rc;
+
+    const float* d_refs = refs ? reinterpret_cast<const float*>(v->d_batch_m + refs_at) : v->d_src;
+    const int64_t src_plane = (int64_t)v->H * v->P, ref_plane = refs ? (int64_t)image : src_plane;
+    int64_t last_cnt = 0;
+    for (int64_t q0 = 0; q0 < units; q0 += per_launch) {
+        last_cnt = std::min(per_launch, units - q0);
+        VT_HIP(launch_correlate_stack(v->d_src, src_plane, v->P, d_refs, ref_plane, refs ? v->W : v->P,
+                                      reinterpret_cast<const CorrEntry*>(v->d_batch_m), res.ptr<double>(), v->d_proj_part, q0, (int)last_cnt, cp,
+                                      v->stream));
+    }
+    const int T[3] = {1, kCorrPiece, kCorrPiece};
+    const int Lds[3] = {1, cp.lds_rows, cp.pitch};
+    record_launch(v, 24, T, Lds, cp.lds_bytes, cp.unit_wgs * last_cnt);
+    return res.finish();
+}
+
 // a float32 batch of n matrices in float64
 std::vector<double> widened(const float* m4x4s, int n)
 {
@@ -3182,6 +3258,12 @@ int vt_volume_filter_stack(vt_volume_t* v, int n, const int32_t* planes, const d
                            const double* weights, float* out, int flags)
 {
     return do_filter_stack(v, n, planes, taps, n_taps, k, axis, pad, weights, out, flags);
+}
+
+int vt_volume_correlate_stack(vt_volume_t* v, int n, const int32_t* planes, const float* refs, int n_refs, const int32_t* ref_planes,
+                              int grid_h, int grid_w, int r_h, int r_w, double* out, int flags)
+{
+    return do_correlate_stack(v, n, planes, refs, n_refs, ref_planes, grid_h, grid_w, r_h, r_w, out, flags);
 }
 
 int vt_volume_extract_dot(vt_volume_t* v, int n, const float* m4x4s, const float* tmpl, const float* mask, int box_d, int box_h, int box_w,

@@ -449,6 +449,38 @@ inline int64_t filter_stack_segments(int L) { return ((int64_t)L + kFilterSeg - 
 hipError_t launch_filter_stack(const float* src, float* out, const FilterEntry* d_tab, const FilterTap* d_taps, const double* d_rows, int n,
                                int H, int W, int P, int axis, int pad, int k, hipStream_t stream);
 
+// shift scores of every image of the stack against a reference, per patch of a grid (vt_kernels_correlatestack.hip, kind 24).  A patch
+// is cut from its own origin into pieces of kCorrPiece x kCorrPiece pixels, the shift window into blocks of rows_blk shift rows x
+// runs * cv shift columns; one workgroup per (entry, patch, piece, block), entry-major, blocks fastest.  Every patch of a call gets
+// the piece grid of the largest patch; a piece past a smaller patch's end adds +0.
+constexpr int kCorrPiece = 64;                 // piece edge: 4 bands of kCorrBand rows, one per wave
+constexpr int kCorrBand = 16;
+constexpr int kCorrGroup = 8;                  // reference pixels served by one register window
+constexpr int kCorrMaxRuns = 7;                // runs of cv column shifts side by side in a wave
+constexpr int kCorrRefBytes = kCorrPiece * kCorrPiece * 4;
+struct CorrEntry {
+    int32_t plane;             // the image
+    int32_t ref;               // the reference: index among the uploaded references, or the resident image
+};
+static_assert(sizeof(CorrEntry) == 8, "one entry per double of the staging vector");
+struct CorrPlan {
+    int H, W, gh, gw, rh, rw, nu, nv;          // image, grid, window, shifts per axis (2 rh + 1, 2 rw + 1)
+    int pieces_y, pieces_x;                    // pieces per patch
+    int cv, runs, rows_blk;                    // a lane's run of column shifts (9 or 11), runs per shift row, shift rows per block
+    int blocks_u, blocks_v;                    // blocks of the window
+    int lds_rows, pitch;                       // staged image rows (kCorrPiece + rows_blk - 1) and the floats between them
+    int lds_bytes;                             // kCorrRefBytes + lds_rows * pitch * 4
+    int64_t unit_wgs;                          // workgroups per (entry, patch)
+    int64_t unit_part;                         // float64 partials per (entry, patch): pieces * nu * nv, 0 with one piece
+};
+CorrPlan correlate_stack_plan(int H, int W, int gh, int gw, int rh, int rw);
+// units [q0, q0 + count) of the call, unit q = entry q / (gh gw), patch q % (gh gw).  With one piece per patch the scores go to `out`,
+// otherwise the partials of piece k of local unit l go to part[(l * pieces + k) * nu * nv ...] and a second launch adds them in
+// ascending k into `out`.
+hipError_t launch_correlate_stack(const float* src, int64_t src_plane, int src_pitch, const float* refs, int64_t ref_plane, int ref_pitch,
+                                  const CorrEntry* d_tab, double* out, double* part, int64_t q0, int count, const CorrPlan& cp,
+                                  hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

@@ -15,7 +15,7 @@ from scipy.ndimage import affine_transform, convolve1d, map_coordinates, spline_
 from . import _native
 from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
 from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, place_matrices, tilt_matrices,
-                    backproject_matrices, backproject_box_matrices, stack_matrices, ramp_taps,
+                    backproject_matrices, backproject_box_matrices, stack_matrices, ramp_taps, patch_bounds, peak_shifts,
                     get_available_devices, switch_to_device)
 from .utils.matrices import _box_shape
 
@@ -1427,6 +1427,142 @@ class StaticVolume:
             raise ValueError('tilt_axis must be 1 or 2')
         axis = 3 - tilt_axis
         return self.filter_stack(ramp_taps(self.shape[axis], window, half_width), axis, weights, pad, False, output)
+
+    # -- shift scores of the stack against references (extension: where align_stack's shifts and warp_stack's grids come from) ----
+    def correlate_stack(self, references=None, max_shift=(8, 8), patch_grid=(1, 1), profile: bool = False, output=None, *,
+                        planes=None, reference_planes=None, _flags: int = 0) -> Union[np.ndarray, None]:
+        """This volume taken as a stack of ``T`` images ``(T, H, W)``, each cross-correlated with a reference over the window of integer
+        shifts ``max_shift = (Rh, Rw)``, per patch of ``patch_grid = (gH, gW)``:
+        ``out[i, a, b, u, v] = sum over (y, x) in patch (a, b) of reference_i[y, x] * image_i[y + u - Rh, x + v - Rw]``, the image read
+        as 0 outside, summed in float64.  Patch ``(a, b)`` covers rows ``[a H // gH, (a + 1) H // gH)`` and columns ``[b W // gW, (b + 1)
+        W // gW)`` (``utils.patch_bounds``); ``1 <= gH <= H``, ``1 <= gW <= W``, ``0 <= Rh <= H - 1``, ``0 <= Rw <= W - 1``.  Exactly one
+        of ``references`` and ``reference_planes`` must be given: ``references`` is ``(H, W)`` (shared by every entry) or ``(n, H, W)``,
+        taken as float32 and finite; ``reference_planes`` are ``n`` indices of images of this stack (a tilt against its neighbour:
+        nothing is uploaded).  ``planes``: ``n`` image indices inside ``[0, T)``; None = ``0 .. n-1``, and then ``n`` must equal ``T``
+        (``n`` is the number of references if there are several, else of reference planes, else of planes, else ``T``).  The volume must
+        hold samples: a ``filt_*`` interpolation is refused; ``stack=True`` is not needed.  Returns a float64 array ``(n, gH, gW, 2 Rh +
+        1, 2 Rw + 1)``, or fills ``output`` of that shape (C-contiguous numpy float64, or a torch-ROCm float64 tensor on the volume's device) and returns None
+        on a GPU device.  On a GPU device every product is exact, the additions follow a fixed order that depends on the patch's rows
+        and columns alone, a score does not depend on the rest of the batch, the other patches or the window, and repeated calls give
+        identical bits; a zero outside the image is multiplied, not skipped, so a non-finite reference pixel makes every score of its
+        patch non-finite.  ``device='cpu'`` evaluates the same definition in float64 numpy, one sliced product-sum per shift (a shift's
+        samples outside the image are left out there, which differs for non-finite references only)."""
+        T, H, W = (int(s) for s in self.shape)
+        if (references is None) == (reference_planes is None):
+            raise ValueError('exactly one of references and reference_planes must be given')
+
+        def pair(val, name):
+            try:
+                a, b = val
+            except (TypeError, ValueError):
+                raise ValueError(f'{name} must be a pair of ints') from None
+            for x in (a, b):
+                if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+                    raise ValueError(f'{name} must be a pair of ints')
+            return int(a), int(b)
+        rh, rw = pair(max_shift, 'max_shift')
+        gh, gw = pair(patch_grid, 'patch_grid')
+        if not (0 <= rh <= H - 1 and 0 <= rw <= W - 1):
+            raise ValueError(f'max_shift must lie inside [0, {H - 1}] x [0, {W - 1}]')
+        if not (1 <= gh <= H and 1 <= gw <= W):
+            raise ValueError(f'patch_grid must lie inside [1, {H}] x [1, {W}]')
+        refs = shared = None
+        if references is not None:
+            refs = np.asarray(references, dtype=np.float32)
+            if refs.ndim not in (2, 3) or refs.shape[-2:] != (H, W) or refs.shape[0] == 0:
+                raise ValueError(f'references must have shape ({H}, {W}) or (n, {H}, {W})')
+            shared = refs.ndim == 2
+            refs = np.ascontiguousarray(refs)
+            if not np.isfinite(refs).all():
+                raise ValueError('references must be finite')
+
+        def indices(val, name):
+            a = np.asarray(val)
+            if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f'{name} must be a vector of integers')
+            if a.min() < 0 or a.max() >= T:
+                raise ValueError(f'{name} must lie inside [0, {T})')
+            return np.ascontiguousarray(a, dtype=np.int32)
+        pl = None if planes is None else indices(planes, 'planes')
+        rp = None if reference_planes is None else indices(reference_planes, 'reference_planes')
+        if refs is not None and not shared:
+            n = refs.shape[0]
+        elif rp is not None:
+            n = rp.shape[0]
+        elif pl is not None:
+            n = pl.shape[0]
+        else:
+            n = T
+        if pl is None and n != T:
+            raise ValueError(f'{n} entries for a stack of {T} images: planes must be given')
+        if pl is not None and pl.shape[0] != n:
+            raise ValueError(f'{pl.shape[0]} planes for {n} entries')
+        shape = (n, gh, gw, 2 * rh + 1, 2 * rw + 1)
+        if int(np.prod(shape, dtype=np.float64)) >= 2 ** 31:
+            raise ValueError(f'an output of shape {shape} has 2^31 elements or more')
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.interpolation.startswith('filt_'):
+            raise ValueError('correlate_stack needs samples, and a filt_* volume holds prefilter coefficients: correlate on a linear volume')
+        if self.device == 'cpu':
+            if output is not None and not (isinstance(output, np.ndarray) and output.dtype == np.float64):
+                raise ValueError(f'output must be a float64 array of shape {shape}')
+            t_start = time.time()
+            res = np.zeros(shape, dtype=np.float64)
+            ye, xe = patch_bounds(H, gh), patch_bounds(W, gw)
+            for i in range(n):
+                img = np.asarray(self.data[i if pl is None else int(pl[i])], dtype=np.float32).astype(np.float64)
+                if rp is not None:
+                    ref = np.asarray(self.data[int(rp[i])], dtype=np.float32).astype(np.float64)
+                else:
+                    ref = (refs if shared else refs[i]).astype(np.float64)
+                for a in range(gh):
+                    for b in range(gw):
+                        y0, y1, x0, x1 = int(ye[a]), int(ye[a + 1]), int(xe[b]), int(xe[b + 1])
+                        for u in range(2 * rh + 1):
+                            ya, yb = max(y0, rh - u), min(y1, H + rh - u)          # reference rows whose sample lies inside the image
+                            if ya >= yb:
+                                continue
+                            for v in range(2 * rw + 1):
+                                xa, xb = max(x0, rw - v), min(x1, W + rw - v)
+                                if xa < xb:
+                                    res[i, a, b, u, v] = (ref[ya:yb, xa:xb] * img[ya + u - rh:yb + u - rh, xa + v - rw:xb + v - rw]).sum()
+            if profile:
+                print(f'{n} images correlated in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = np.empty(shape, dtype=np.float64)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev, dtype=np.float64)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        _native.check(self._lib.vt_volume_correlate_stack(self._handle, n, None if pl is None else pl.ctypes.data,
+                                                          None if refs is None else refs.ctypes.data,
+                                                          0 if refs is None else (1 if shared else n),
+                                                          None if rp is None else rp.ctypes.data, gh, gw, rh, rw, ptr, flags),
+                      'vt_volume_correlate_stack')
+        if profile:
+            print(f'{n} images correlated in {self.timer_stop():.3f}ms')
+        return result
+
+    def find_shifts(self, references=None, max_shift=(8, 8), patch_grid=(1, 1), subpixel: bool = True, *, planes=None,
+                    reference_planes=None) -> np.ndarray:
+        """Where every image, or every patch of it, matches its reference best: ``utils.peak_shifts(correlate_stack(...), subpixel)``,
+        float64 ``(n, gH, gW, 2)``.  Entry ``[i, a, b]`` is the displacement ``d = (dy, dx)`` with ``image_i[y + d] ~ reference_i[y]`` on
+        patch ``(a, b)``, searched inside ``max_shift`` and refined by a three-point parabola per axis.  ``align_stack(shifts=-d[:, 0,
+        0])`` moves the images back onto their references, and ``d`` itself is ``warp_stack``'s displacement for that patch: an output
+        pixel ``y`` of the patch samples the image at ``y + d``.  The values belong to the patch centres, which are not ``warp_stack``'s
+        nodes -- those span the image corner to corner (``utils.stack_grid_nodes``) -- so a grid for ``warp_stack`` is interpolated or
+        extrapolated from them."""
+        return peak_shifts(self.correlate_stack(references, max_shift, patch_grid, planes=planes, reference_planes=reference_planes), subpixel)
 
     def translate(self, translation: Vec3, profile: bool = False, output=None):
         return self.affine(translation_matrix(translation), profile, output)
