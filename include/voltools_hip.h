@@ -102,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack), 23 a 1-D filter along axis 1 or 2 of every image of a stack (one workgroup per (entry, strip of lines, segment of the filtered axis), float64 sums over the non-zero taps; vt_volume_filter_stack), 24 shift scores of every image of a stack against a reference per patch of a grid (one workgroup per (entry, patch, piece of 64 x 64 pixels, block of shifts), float64 sums, pieces added by a second launch; vt_volume_correlate_stack) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack), 23 a 1-D filter along axis 1 or 2 of every image of a stack (one workgroup per (entry, strip of lines, segment of the filtered axis), float64 sums over the non-zero taps; vt_volume_filter_stack), 24 shift scores of every image of a stack against a reference per patch of a grid (one workgroup per (entry, patch, piece of 64 x 64 pixels, block of shifts), float64 sums, pieces added by a second launch; vt_volume_correlate_stack), 25 the sum and the sum of squares of the samples under every patch of a grid at every shift, for every image of a stack (row sums per (entry, block of image rows, patch column, block of column shifts), then one thread per value adds its patch's rows; vt_volume_moments_stack) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -606,6 +606,52 @@ int vt_volume_correlate_stack(vt_volume_t* vol, int n, const int32_t* planes /* 
                               const float* refs /* n_refs x H x W, or NULL */, int n_refs /* 1 or n; 0 with ref_planes */,
                               const int32_t* ref_planes /* n, or NULL */, int grid_h, int grid_w, int r_h, int r_w,
                               double* out /* n x grid_h x grid_w x (2 r_h + 1) x (2 r_w + 1) */, int flags);
+
+/* ---- moments_stack: the sum and the sum of squares of the samples that lie under every patch at every shift of vt_volume_correlate_stack's
+ * window -- with the reference's own two sums, what turns a raw score into a correlation coefficient (voltools_amd.utils.
+ * normalized_scores).  The handle, the entries, the patch grid and the window follow vt_volume_correlate_stack's rules word for word:
+ * samples S (T, H, W); entry i is image p = planes[i] (NULL: image i, n = T); patch (a, b) of the grid (grid_h, grid_w), 1 <= grid_h <= H
+ * and 1 <= grid_w <= W, covers rows [a H / grid_h, (a+1) H / grid_h) and columns [b W / grid_w, (b+1) W / grid_w) by floor division;
+ * the window is (r_h, r_w), 0 <= r_h <= H - 1 and 0 <= r_w <= W - 1.
+ *     out[i, a, b, u, v, 0] = sum over (y, x) in patch (a, b) of  (double) s(y + u - r_h, x + v - r_w)
+ *     out[i, a, b, u, v, 1] = the same sum of                     (double) s(..)^2
+ *     s(y', x') = S[p, y', x'] inside the image, +0 outside
+ * out: float64, n x grid_h x grid_w x (2 r_h + 1) x (2 r_w + 1) x 2 in C order, host memory or device memory with VT_OUT_DEVICE.  Every
+ * square is exact in float64 (the factor carries 24 bits); every addition is rounded.  Every sum starts from +0, and the order of
+ * additions is a fixed expression of the patch's own rows and columns, the shift and (H, W):
+ *   - a row sum R[y', b, dv], for image row y' in [0, H), patch column b and column displacement dv = v - r_w, starts from +0 and takes
+ *     the samples s(y', x + dv) of the patch's columns x in ascending order, acc0 = acc0 + s and acc1 = fma(s, s, acc1); a sample
+ *     outside the image is +0;
+ *   - out[i, a, b, u, v, k] starts from +0 and takes the row sums R[y + u - r_h, b, v - r_w][k] of the patch's rows y in ascending
+ *     order; a row outside the image is +0.
+ * Every value is a plain sum of its own samples: there are no running sums that add the entering sample and subtract the leaving one.
+ * A value therefore does not depend on n, on the other entries or its place in the batch, on the other patches, on r_h and r_w beyond
+ * the shift lying inside the window, on host versus device output, on earlier calls or on recycled memory; repeated calls give identical
+ * bits.  No atomics, no memset.  A non-finite image pixel reaches exactly the (patch, shift) pairs whose window covers it, and no
+ * others.  out[.., 0] equals vt_volume_correlate_stack against a reference of ones, and out[.., 1] the same on a handle holding the
+ * squared samples, up to the rounding of the two orders of addition (exactly, where every partial sum is exact); the work here is
+ * pixels x (2 r_w + 1) additions and fmas, not pixels x shifts.
+ * TWO launches per run of entries (last_kernel 25).  The first forms the row sums: one workgroup per (entry, block of rows_wg image
+ * rows, patch column, block of column shifts).  A lane owns one image row and a run of cv consecutive column shifts as 2 cv float64
+ * accumulators, cv = 11 if that pads 2 r_w + 1 to fewer columns than 9 does, else 9; runs = min(7, ceil((2 r_w + 1) / cv)) runs lie
+ * side by side in a wave, which holds 64 / runs rows, and rows_wg = 4 x (64 / runs); a block of column shifts is runs cv wide and a
+ * wider window goes onto the grid.  The workgroup walks its patch column in chunks of 32 pixels and stages, per chunk, rows_wg rows
+ * of 31 + runs cv samples at a pitch of 32 + runs cv floats, zeros outside the image included: last_tile = (1, rows_wg, 32),
+ * last_lds_dims = (1, rows_wg, 32 + runs cv), last_lds_bytes = 4 x rows_wg x pitch, at most 44032.  The second launch has one thread
+ * per value.  last_grid = the workgroups of the first launch of the call's last run of entries, entries of it x ceil(H / rows_wg) x
+ * grid_w x blocks of column shifts.  A call whose row sums (H x grid_w x (2 r_w + 1) x 16 bytes per entry) would exceed 64 MiB is
+ * split into runs of entries inside the call, one entry per run at least.
+ * Every flag but VT_OUT_DEVICE is ignored.  Device memory beyond the source: 8 bytes per entry, in the table buffer, and the row sums,
+ * in the buffer the handle recycles for partial sums.
+ * Bounds (VT_EUNSUPPORTED beyond, decided before any array is read): n x grid_h x grid_w x (2 r_h + 1) x (2 r_w + 1) x 2 < 2^31 output
+ * elements; the workgroups of one entry < 2^31 (more than that in a call are split into runs of entries) and H x grid_w x (2 r_w + 1) x
+ * 2 < 2^31 row sums per entry.  filt_* handles hold
+ * prefilter coefficients and are refused with VT_EUNSUPPORTED, as are VT_EDGE_SCIPY handles; VT_STACK is not required.  Slab handles
+ * and handles not yet finalized, n <= 0, a plane outside [0, T), planes == NULL with n != T, a grid or window outside the ranges above,
+ * NULL vol / out: VT_EINVAL.  Host `out`: returns after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  The
+ * handle's output shape is neither read nor changed.  A refusal leaves the handle usable. */
+int vt_volume_moments_stack(vt_volume_t* vol, int n, const int32_t* planes /* n, or NULL */, int grid_h, int grid_w, int r_h, int r_w,
+                            double* out /* n x grid_h x grid_w x (2 r_h + 1) x (2 r_w + 1) x 2 */, int flags);
 
 /* ---- projection: the transformed volume summed over axis 0, without materialising it ----
  * Replaces `static_volume.transform(...).sum(axis=0)` of examples/projections.py:20-26 (a cupy reduction after the

@@ -2801,6 +2801,60 @@ int do_correlate_stack(vt_volume* v, int n, const int32_t* planes, const float* 
     return res.finish();
 }
 
+// n x gh x gw x (2 rh + 1) x (2 rw + 1) x 2 float64: for entry i, patch (a, b) of the grid and shift (u, v), the sum and the sum of
+// squares of image planes[i] under the patch displaced by (u - rh, v - rw), zeros outside the image (vt_kernels_momentsstack.hip has
+// the expression and the order of additions).  Launches of kernel 25 over runs of entries whose row sums stay within the cap, each
+// followed by the launch that adds the rows.  Does not read or change the handle's own output shape.
+int do_moments_stack(vt_volume* v, int n, const int32_t* planes, int gh, int gw, int rh, int rw, double* out, int flags)
+{
+    if (!v || !out) return fail(VT_EINVAL, "NULL argument");
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_whole_volume(v, "moments_stack"))) return rc;
+    if (v->edge_pad) return fail(VT_EUNSUPPORTED, "moments_stack is not available on VT_EDGE_SCIPY handles");
+    if (is_filtered(v->interp))
+        return fail(VT_EUNSUPPORTED, "the handle holds prefilter coefficients, not samples: take moments on a linear handle");
+    if (gh < 1 || gh > v->H || gw < 1 || gw > v->W) return fail(VT_EINVAL, "patch grid (%d,%d) for images of (%d,%d)", gh, gw, v->H, v->W);
+    if (rh < 0 || rh > v->H - 1 || rw < 0 || rw > v->W - 1)
+        return fail(VT_EINVAL, "shift window (%d,%d) for images of (%d,%d): at most (%d,%d)", rh, rw, v->H, v->W, v->H - 1, v->W - 1);
+    // the bounds, before anything of the caller's arrays is read
+    if (rh >= (1 << 29) || rw >= (1 << 29)) return fail(VT_EUNSUPPORTED, "output too large (a window of (%d,%d))", rh, rw);
+    const MomPlan mp = moments_stack_plan(v->H, v->W, gh, gw, rh, rw);
+    const int64_t nunv2 = (int64_t)mp.nu * mp.nv * 2;                  // < 2^62
+    const int64_t per = (int64_t)gh * gw;                              // patches per entry
+    if (nunv2 > 0x7fffffffLL || per > 0x7fffffffLL || per * nunv2 > 0x7fffffffLL || per * nunv2 * n > 0x7fffffffLL)
+        return fail(VT_EUNSUPPORTED, "output too large (%d entries x %lld patches x %lld shifts x 2)", n, (long long)per,
+                    (long long)(nunv2 / 2));
+    if (mp.unit_wgs > 0x7fffffffLL || mp.unit_part > 0x7fffffffLL)
+        return fail(VT_EUNSUPPORTED, "%lld workgroups and %lld row sums per entry", (long long)mp.unit_wgs, (long long)mp.unit_part);
+    if ((rc = select_device(v)) || (rc = check_planes(v, n, planes, ""))) return rc;
+
+    // the call's table: one MomEntry per entry
+    if ((rc = begin_tables(v, (size_t)n))) return rc;
+    MomEntry* const e = reinterpret_cast<MomEntry*>(v->h_batch_m.data());
+    for (int i = 0; i < n; ++i) {
+        e[i].plane = planes ? planes[i] : i;
+        e[i].pad = 0;
+    }
+    // entries per launch: their row sums stay within the cap (one entry's at least), the grid within 2^31
+    int64_t per_launch = std::min<int64_t>(n, 0x7fffffffLL / mp.unit_wgs);
+    per_launch = std::min<int64_t>(per_launch, std::max<int64_t>(1, v->tune.dot_part_cap / (mp.unit_part * (int64_t)sizeof(double))));
+    if ((rc = ensure_partials(v, (size_t)per_launch * (size_t)mp.unit_part * sizeof(double))) || (rc = upload_tables(v))) return rc;
+    ResultScope res(v, out, (size_t)(per * nunv2 * n) * sizeof(double), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open())) return rc;
+
+    const int64_t src_plane = (int64_t)v->H * v->P;
+    int64_t last_cnt = 0;
+    for (int64_t e0 = 0; e0 < n; e0 += per_launch) {
+        last_cnt = std::min<int64_t>(per_launch, n - e0);
+        VT_HIP(launch_moments_stack(v->d_src, src_plane, v->P, reinterpret_cast<const MomEntry*>(v->d_batch_m), res.ptr<double>(),
+                                    v->d_proj_part, e0, (int)last_cnt, mp, v->stream));
+    }
+    const int T[3] = {1, mp.rows_wg, kMomChunk};
+    const int Lds[3] = {1, mp.rows_wg, mp.pitch};
+    record_launch(v, 25, T, Lds, mp.lds_bytes, mp.unit_wgs * last_cnt);
+    return res.finish();
+}
+
 // a float32 batch of n matrices in float64
 std::vector<double> widened(const float* m4x4s, int n)
 {
@@ -3264,6 +3318,11 @@ int vt_volume_correlate_stack(vt_volume_t* v, int n, const int32_t* planes, cons
                               int grid_h, int grid_w, int r_h, int r_w, double* out, int flags)
 {
     return do_correlate_stack(v, n, planes, refs, n_refs, ref_planes, grid_h, grid_w, r_h, r_w, out, flags);
+}
+
+int vt_volume_moments_stack(vt_volume_t* v, int n, const int32_t* planes, int grid_h, int grid_w, int r_h, int r_w, double* out, int flags)
+{
+    return do_moments_stack(v, n, planes, grid_h, grid_w, r_h, r_w, out, flags);
 }
 
 int vt_volume_extract_dot(vt_volume_t* v, int n, const float* m4x4s, const float* tmpl, const float* mask, int box_d, int box_h, int box_w,

@@ -53,7 +53,7 @@ struct Tuning {
     int span = 1;                  // VT_SPAN=0: trilinear general matrices on round 1's packed-footprint kernel (vt_kernels_packed.hip) instead of round 5's (A/B)
     int span_pipe = 0;             // VT_SPAN_PIPE: 1 / 0 = trilinear general matrices on the software-pipelined / the single-buffer form of the packed-span kernel, -1 = the planner's cost model
     int block_th = 8;              // VT_BLOCK_TH: tile height of the lane-block kernel: 8 (8 x 8 x 16 tiles, four workgroups per CU; boxes beyond 40 KiB fall back to 16) or 16 (8 x 16 x 16, two per CU)
-    int64_t dot_part_cap = 64ll << 20;   // VT_DOT_PART_CAP: bytes of float64 partials one launch of the per-box score kernels (kinds 14-16) or of the shift-score kernel (kind 24) may use (tests of the split)
+    int64_t dot_part_cap = 64ll << 20;   // VT_DOT_PART_CAP: bytes of float64 partials one launch of the per-box score kernels (kinds 14-16) or of the shift-score kernel (kind 24) may use, and of float64 row sums one run of entries of the window-sum kernel (kind 25) (tests of the split)
     void read()
     {
         auto num = [](const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; };

@@ -481,6 +481,35 @@ hipError_t launch_correlate_stack(const float* src, int64_t src_plane, int src_p
                                   const CorrEntry* d_tab, double* out, double* part, int64_t q0, int count, const CorrPlan& cp,
                                   hipStream_t stream);
 
+// window sums of every image of the stack, per patch of a grid: the sum and the sum of squares of the samples under the patch at every
+// shift (vt_kernels_momentsstack.hip, kind 25).  Two launches per run of entries: row sums R[entry, image row, patch column, column
+// shift, 2] into the handle's partials, then every output as the ascending sum of its patch's rows of R.  The first launch has one
+// workgroup per (entry, block of rows_wg image rows, patch column, block of runs * cv column shifts), entry-major, blocks fastest; a
+// workgroup walks its patch column in chunks of kMomChunk pixels.
+constexpr int kMomChunk = 32;                  // patch columns staged at a time
+constexpr int kMomGroup = 8;                   // pixels served by one register window
+constexpr int kMomMaxRuns = 7;                 // runs of cv column shifts side by side in a wave
+struct MomEntry {
+    int32_t plane;             // the image
+    int32_t pad;
+};
+static_assert(sizeof(MomEntry) == 8, "one entry per double of the staging vector");
+struct MomPlan {
+    int H, W, gh, gw, rh, rw, nu, nv;          // image, grid, window, shifts per axis (2 rh + 1, 2 rw + 1)
+    int cv, runs;                              // a lane's run of column shifts (9 or 11), runs per image row
+    int rows_wave, rows_wg;                    // image rows per wave (64 / runs) and per workgroup (4 waves)
+    int row_blocks, blocks_v;                  // blocks of image rows, blocks of column shifts
+    int pitch;                                 // floats between staged rows: kMomChunk + runs * cv
+    int lds_bytes;                             // rows_wg * pitch * 4
+    int64_t unit_wgs;                          // workgroups of the first launch per entry: row_blocks * gw * blocks_v
+    int64_t unit_part;                         // float64 row sums per entry: H * gw * nv * 2
+};
+MomPlan moments_stack_plan(int H, int W, int gh, int gw, int rh, int rw);
+// entries [e0, e0 + count) of the call: the row sums of local entry l go to part[l * unit_part ...], the sums of entry e0 + l to
+// out[(e0 + l) * gh * gw * nu * nv * 2 ...].
+hipError_t launch_moments_stack(const float* src, int64_t src_plane, int src_pitch, const MomEntry* d_tab, double* out, double* part,
+                                int64_t e0, int count, const MomPlan& mp, hipStream_t stream);
+
 // prefilter (vt_kernels_prefilter.hip).  src -> dst; `*in_place_ok` tells whether src == dst is legal.
 // axis: 0 (Z, stride H*W), 1 (Y, stride W), 2 (X, contiguous).
 hipError_t launch_prefilter_axis(int axis, const float* src, float* dst, int D, int H, int W, int pitch,

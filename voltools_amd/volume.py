@@ -15,7 +15,7 @@ from scipy.ndimage import affine_transform, convolve1d, map_coordinates, spline_
 from . import _native
 from .transforms import affine as _affine, AVAILABLE_INTERPOLATIONS, _INTERPOLATIONS, _triple, _scipy_arguments
 from .utils import (scale_matrix, shear_matrix, rotation_matrix, translation_matrix, transform_matrix, box_matrices, place_matrices, tilt_matrices,
-                    backproject_matrices, backproject_box_matrices, stack_matrices, ramp_taps, patch_bounds, peak_shifts,
+                    backproject_matrices, backproject_box_matrices, stack_matrices, ramp_taps, patch_bounds, peak_shifts, patch_moments, normalized_scores,
                     get_available_devices, switch_to_device)
 from .utils.matrices import _box_shape
 
@@ -63,6 +63,36 @@ def _warp_stack_coordinates(disp: np.ndarray, m: np.ndarray, shape):
     yy = (m[1, 1] * h[:, None] + (m[1, 2] * w[None, :] + m[1, 3])) + u[..., 0]
     xx = (m[2, 1] * h[:, None] + (m[2, 2] * w[None, :] + m[2, 3])) + u[..., 1]
     return yy, xx
+
+
+def _window_and_grid(max_shift, patch_grid, H: int, W: int):
+    """``((Rh, Rw), (gH, gW))`` of the stack calls that take a shift window and a patch grid, checked against images ``(H, W)``."""
+    def pair(val, name):
+        try:
+            a, b = val
+        except (TypeError, ValueError):
+            raise ValueError(f'{name} must be a pair of ints') from None
+        for x in (a, b):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+                raise ValueError(f'{name} must be a pair of ints')
+        return int(a), int(b)
+    rh, rw = pair(max_shift, 'max_shift')
+    gh, gw = pair(patch_grid, 'patch_grid')
+    if not (0 <= rh <= H - 1 and 0 <= rw <= W - 1):
+        raise ValueError(f'max_shift must lie inside [0, {H - 1}] x [0, {W - 1}]')
+    if not (1 <= gh <= H and 1 <= gw <= W):
+        raise ValueError(f'patch_grid must lie inside [1, {H}] x [1, {W}]')
+    return (rh, rw), (gh, gw)
+
+
+def _plane_indices(val, name: str, T: int) -> np.ndarray:
+    """A non-empty vector of image indices inside ``[0, T)`` as contiguous int32."""
+    a = np.asarray(val)
+    if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f'{name} must be a vector of integers')
+    if a.min() < 0 or a.max() >= T:
+        raise ValueError(f'{name} must lie inside [0, {T})')
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 class StaticVolume:
@@ -1451,21 +1481,7 @@ class StaticVolume:
         if (references is None) == (reference_planes is None):
             raise ValueError('exactly one of references and reference_planes must be given')
 
-        def pair(val, name):
-            try:
-                a, b = val
-            except (TypeError, ValueError):
-                raise ValueError(f'{name} must be a pair of ints') from None
-            for x in (a, b):
-                if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-                    raise ValueError(f'{name} must be a pair of ints')
-            return int(a), int(b)
-        rh, rw = pair(max_shift, 'max_shift')
-        gh, gw = pair(patch_grid, 'patch_grid')
-        if not (0 <= rh <= H - 1 and 0 <= rw <= W - 1):
-            raise ValueError(f'max_shift must lie inside [0, {H - 1}] x [0, {W - 1}]')
-        if not (1 <= gh <= H and 1 <= gw <= W):
-            raise ValueError(f'patch_grid must lie inside [1, {H}] x [1, {W}]')
+        (rh, rw), (gh, gw) = _window_and_grid(max_shift, patch_grid, H, W)
         refs = shared = None
         if references is not None:
             refs = np.asarray(references, dtype=np.float32)
@@ -1475,16 +1491,8 @@ class StaticVolume:
             refs = np.ascontiguousarray(refs)
             if not np.isfinite(refs).all():
                 raise ValueError('references must be finite')
-
-        def indices(val, name):
-            a = np.asarray(val)
-            if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
-                raise ValueError(f'{name} must be a vector of integers')
-            if a.min() < 0 or a.max() >= T:
-                raise ValueError(f'{name} must lie inside [0, {T})')
-            return np.ascontiguousarray(a, dtype=np.int32)
-        pl = None if planes is None else indices(planes, 'planes')
-        rp = None if reference_planes is None else indices(reference_planes, 'reference_planes')
+        pl = None if planes is None else _plane_indices(planes, 'planes', T)
+        rp = None if reference_planes is None else _plane_indices(reference_planes, 'reference_planes', T)
         if refs is not None and not shared:
             n = refs.shape[0]
         elif rp is not None:
@@ -1553,16 +1561,123 @@ class StaticVolume:
             print(f'{n} images correlated in {self.timer_stop():.3f}ms')
         return result
 
+    # -- window sums of the stack (extension: what turns correlate_stack's scores into correlation coefficients) ----
+    def moments_stack(self, max_shift=(8, 8), patch_grid=(1, 1), profile: bool = False, output=None, *, planes=None,
+                      _flags: int = 0) -> Union[np.ndarray, None]:
+        """This volume taken as a stack of ``T`` images ``(T, H, W)``: the sum and the sum of squares of the samples that lie under
+        every patch of ``patch_grid = (gH, gW)`` at every shift of the window ``max_shift = (Rh, Rw)``,
+        ``out[i, a, b, u, v, 0] = sum over (y, x) in patch (a, b) of image_i[y + u - Rh, x + v - Rw]`` and ``out[i, a, b, u, v, 1]`` the
+        same sum of the squares, the image read as 0 outside, summed in float64: the two sums of the image that stand beside
+        ``correlate_stack``'s score in a correlation coefficient (``utils.normalized_scores``).  The patches, the window, their ranges
+        and ``planes`` are ``correlate_stack``'s: ``planes`` are ``n`` image indices inside ``[0, T)``; None = every image in order.
+        The volume must hold samples: a ``filt_*`` interpolation is refused; ``stack=True`` is not needed.  Returns a float64 array
+        ``(n, gH, gW, 2 Rh + 1, 2 Rw + 1, 2)``, or fills ``output`` of that shape (C-contiguous numpy float64, or a torch-ROCm float64
+        tensor on the volume's device) and returns None on a GPU device.  On a GPU device every square is exact, the additions follow
+        a fixed order (row sums over the patch's columns, then over its rows) that depends on the patch's rows and columns and the shift
+        alone, every value is a plain sum of its own samples (no running sums), so a value does not depend on the rest of the batch, the
+        other patches or the window, a non-finite pixel reaches exactly the (patch, shift) pairs whose window covers it, and repeated
+        calls give identical bits.  The work is pixels x (2 Rw + 1) additions, not pixels x shifts.  ``device='cpu'`` evaluates the same
+        definition in float64 numpy."""
+        T, H, W = (int(s) for s in self.shape)
+        (rh, rw), (gh, gw) = _window_and_grid(max_shift, patch_grid, H, W)
+        pl = None if planes is None else _plane_indices(planes, 'planes', T)
+        n = T if pl is None else pl.shape[0]
+        shape = (n, gh, gw, 2 * rh + 1, 2 * rw + 1, 2)
+        if int(np.prod(shape, dtype=np.float64)) >= 2 ** 31:
+            raise ValueError(f'an output of shape {shape} has 2^31 elements or more')
+        if output is not None and tuple(getattr(output, 'shape', ())) != shape:
+            raise ValueError(f'output must have shape {shape}')
+        if self.interpolation.startswith('filt_'):
+            raise ValueError('moments_stack needs samples, and a filt_* volume holds prefilter coefficients: take moments on a linear volume')
+        if self.device == 'cpu':
+            if output is not None and not (isinstance(output, np.ndarray) and output.dtype == np.float64):
+                raise ValueError(f'output must be a float64 array of shape {shape}')
+            t_start = time.time()
+            res = np.empty(shape, dtype=np.float64)
+            ye, xe = patch_bounds(H, gh)[:-1], patch_bounds(W, gw)[:-1]
+            done = {}
+            for i in range(n):
+                p = i if pl is None else int(pl[i])
+                if p in done:
+                    res[i] = res[done[p]]
+                    continue
+                done[p] = i
+                padded = np.zeros((H + 2 * rh, W + 2 * rw), dtype=np.float64)
+                padded[rh:rh + H, rw:rw + W] = np.asarray(self.data[p], dtype=np.float32)
+                with np.errstate(invalid='ignore', over='ignore'):
+                    for k, field in enumerate((padded, padded * padded)):
+                        # column sums per patch column and column shift first, as the device does, then the rows per row shift
+                        rows = np.stack([np.add.reduceat(field[:, v:v + W], xe, axis=1) for v in range(2 * rw + 1)], axis=-1)
+                        for u in range(2 * rh + 1):
+                            res[i, :, :, u, :, k] = np.add.reduceat(rows[u:u + H], ye, axis=0)
+            if profile:
+                print(f'moments of {n} images in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags
+        if output is None:
+            result = np.empty(shape, dtype=np.float64)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, shape, self._dev, dtype=np.float64)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        _native.check(self._lib.vt_volume_moments_stack(self._handle, n, None if pl is None else pl.ctypes.data, gh, gw, rh, rw, ptr, flags),
+                      'vt_volume_moments_stack')
+        if profile:
+            print(f'moments of {n} images in {self.timer_stop():.3f}ms')
+        return result
+
+    def correlate_stack_normalized(self, references=None, max_shift=(8, 8), patch_grid=(1, 1), profile: bool = False, output=None, *,
+                                   planes=None, reference_planes=None) -> Union[np.ndarray, None]:
+        """``correlate_stack``'s scores as correlation coefficients: ``utils.normalized_scores(correlate_stack(...), moments_stack(...),
+        reference moments)``, float64 ``(n, gH, gW, 2 Rh + 1, 2 Rw + 1)`` inside [-1, 1] up to rounding, and exactly 0 where a patch or
+        the samples under it are constant or a sum is not finite.  The arguments are ``correlate_stack``'s.  Samples outside the image
+        count as zeros among the patch's pixels, which is ``correlate_stack``'s own convention: a patch on the image border is pulled
+        towards the shifts that stay inside.  The reference's two sums per patch come from ``utils.patch_moments`` for host
+        ``references`` and, for ``reference_planes`` on a GPU device, from ``moments_stack(max_shift=(0, 0), planes=reference_planes)``, so
+        that nothing is downloaded; the two routes add in different orders and may differ in the last bits.  The scores and the window
+        sums are computed on the device and combined on the host (numpy); ``output`` must be a numpy float64 array of the result's
+        shape, which is filled and returned."""
+        scores = self.correlate_stack(references, max_shift, patch_grid, profile, planes=planes, reference_planes=reference_planes)
+        moments = self.moments_stack(max_shift, patch_grid, profile, planes=planes)
+        if reference_planes is not None:
+            if self.device == 'cpu':
+                ref_moments = patch_moments(np.asarray(self.data, dtype=np.float32)[np.asarray(reference_planes)], patch_grid)
+            else:
+                ref_moments = self.moments_stack((0, 0), patch_grid, planes=reference_planes)[:, :, :, 0, 0, :]
+        else:
+            refs = np.asarray(references, dtype=np.float32)
+            ref_moments = patch_moments(refs[None] if refs.ndim == 2 else refs, patch_grid)
+        ncc = normalized_scores(scores, moments, ref_moments, image_shape=self.shape[1:])
+        if output is None:
+            return ncc
+        if not (isinstance(output, np.ndarray) and output.dtype == np.float64 and output.shape == ncc.shape):
+            raise ValueError(f'output must be a float64 array of shape {ncc.shape}')
+        output[...] = ncc
+        return output
+
     def find_shifts(self, references=None, max_shift=(8, 8), patch_grid=(1, 1), subpixel: bool = True, *, planes=None,
-                    reference_planes=None) -> np.ndarray:
+                    reference_planes=None, normalized: bool = False) -> np.ndarray:
         """Where every image, or every patch of it, matches its reference best: ``utils.peak_shifts(correlate_stack(...), subpixel)``,
         float64 ``(n, gH, gW, 2)``.  Entry ``[i, a, b]`` is the displacement ``d = (dy, dx)`` with ``image_i[y + d] ~ reference_i[y]`` on
         patch ``(a, b)``, searched inside ``max_shift`` and refined by a three-point parabola per axis.  ``align_stack(shifts=-d[:, 0,
         0])`` moves the images back onto their references, and ``d`` itself is ``warp_stack``'s displacement for that patch: an output
         pixel ``y`` of the patch samples the image at ``y + d``.  The values belong to the patch centres, which are not ``warp_stack``'s
         nodes -- those span the image corner to corner (``utils.stack_grid_nodes``) -- so a grid for ``warp_stack`` is interpolated or
-        extrapolated from them."""
-        return peak_shifts(self.correlate_stack(references, max_shift, patch_grid, planes=planes, reference_planes=reference_planes), subpixel)
+        extrapolated from them.  ``normalized=True`` takes the peak of ``correlate_stack_normalized`` instead: the correlation
+        coefficient follows the structure under the patch where the raw score, on images with a positive mean, follows whatever bright
+        thing slides under it."""
+        if normalized:
+            scores = self.correlate_stack_normalized(references, max_shift, patch_grid, planes=planes, reference_planes=reference_planes)
+        else:
+            scores = self.correlate_stack(references, max_shift, patch_grid, planes=planes, reference_planes=reference_planes)
+        return peak_shifts(scores, subpixel)
 
     def translate(self, translation: Vec3, profile: bool = False, output=None):
         return self.affine(translation_matrix(translation), profile, output)
