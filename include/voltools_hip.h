@@ -102,7 +102,7 @@ typedef struct vt_volume_info {
     int32_t interp;
     int32_t depth, height, width;      /* source dims as passed to create (including any slab halo planes; the mirror padding of VT_EDGE_SCIPY handles is not counted) */
     int32_t out_depth, out_height, out_width;
-    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack), 23 a 1-D filter along axis 1 or 2 of every image of a stack (one workgroup per (entry, strip of lines, segment of the filtered axis), float64 sums over the non-zero taps; vt_volume_filter_stack), 24 shift scores of every image of a stack against a reference per patch of a grid (one workgroup per (entry, patch, piece of 64 x 64 pixels, block of shifts), float64 sums, pieces added by a second launch; vt_volume_correlate_stack), 25 the sum and the sum of squares of the samples under every patch of a grid at every shift, for every image of a stack (row sums per (entry, block of image rows, patch column, block of column shifts), then one thread per value adds its patch's rows; vt_volume_moments_stack) */
+    int32_t last_kernel;               /* 0 none, 1 direct, 2 tiled (boxes), 3 tiled axis-0-separable, 4 marching, 5 marching on plane pairs, 6 tiled (packed footprints), 7 fused projection (vt_volume_project), 8 marching on plane quads, 9 lane-block tiles (general matrices), 10 source rows along w (maps that leave axis 2 alone), 11 batched box extraction (LDS tiles; vt_volume_extract), 12 batched projection (LDS tiles summed along the output depth; vt_volume_project_batch), 13 weighted sum of extracted boxes (LDS tiles summed over the matrices; vt_volume_extract_sum), 14 per-box template scores (LDS tiles reduced within each box; vt_volume_extract_dot), 15 per-box scores against k templates (each box staged and sampled once; vt_volume_extract_dot_multi), 16 g weighted sums of the same extracted boxes (each box staged and sampled once per chunk of columns; vt_volume_extract_sum_multi), 17 posed weighted copies summed into one map (LDS tiles summed over each output tile's list of matrices; vt_volume_place), 18 a stack of images back-projected into one volume (2-D LDS patches, two buffers, summed over the images per output tile; vt_volume_backproject), 19 nb boxes of one shape back-projected from one stack (kernel 18 with a box index, one workgroup per (box, box tile); vt_volume_backproject_boxes), 20 resampling through a displacement grid (per output tile: its nodes in LDS, a staged box bounded by their range or a gather from global memory; vt_volume_warp), 21 per-image 2-D transforms of a stack (one workgroup per (entry, 2-D output tile), one LDS patch, one sample per pixel; vt_volume_affine_stack), 22 per-image displacement grids of a stack (kernel 21's workgroups; per tile its nodes in LDS, a patch bounded by their range or a gather from global memory; vt_volume_warp_stack), 23 a 1-D filter along axis 1 or 2 of every image of a stack (one workgroup per (entry, strip of lines, segment of the filtered axis), float64 sums over the non-zero taps; vt_volume_filter_stack), 24 shift scores of every image of a stack against a reference per patch of a grid (one workgroup per (entry, patch, piece of 64 x 64 pixels, block of shifts), float64 sums, pieces added by a second launch; vt_volume_correlate_stack), 25 the sum and the sum of squares of the samples under every patch of a grid at every shift, for every image of a stack (row sums per (entry, block of image rows, patch column, block of column shifts), then one thread per value adds its patch's rows; vt_volume_moments_stack), 26 the images of kind 22 summed under weight columns without being written (one workgroup per (chunk of columns, 2-D output tile) walks the entries with float64 accumulators; vt_volume_warp_stack_sum) */
     int32_t last_tile[3];              /* output tile (TD, TH, TW) of the last tiled launch (marching: G, TH, TW) */
     int32_t last_lds_dims[3];          /* staged source box (Lz, Ly, Lx) (marching: ring slots, Ly, Lx)    */
     int32_t last_lds_bytes;
@@ -519,6 +519,48 @@ int vt_volume_warp_stack_f64(vt_volume_t* vol, int n, const double* m4x4s /* n x
                              const float* grids /* n_grids x grid_h x grid_w x 2 */, int n_grids /* 1 = shared by all entries, or n */,
                              int grid_h, int grid_w, const int32_t* planes /* n, or NULL */, const double* weights /* n, or NULL */,
                              int out_h, int out_w, float* out, int flags);
+
+/* ---- warp_stack_sum: the images vt_volume_warp_stack would write, summed under g weight columns without being written -- the
+ * motion-corrected sum of a movie, its even / odd half sums and exposure-window sums from ONE sampling of every frame.  The arguments
+ * are vt_volume_warp_stack's with two changes: weights is n x g float64 in C order (NULL: one column of ones, then g must be 1), and out
+ * is g images of out_h x out_w float32.  With B_i[h, w] exactly vt_volume_warp_stack's float32 sample -- the same chain, the same grid
+ * rule, the same inside test with 0 outside, the same (floor, fraction), the same route per (entry, tile) --
+ *     out[c, h, w] = float32(b + sum_i W[i, c] * B_i[h, w]),   i ascending
+ * every term added by weighted_add (the product rounded to float64, then the sum rounded), the sum rounded to float32 once; b is +0, or
+ * double(out[c, h, w]) as found with VT_ACCUMULATE (host out: copied in first).  VT_OUT_DEVICE, VT_FORCE_DIRECT and VT_FORCE_TILED are
+ * as in vt_volume_warp_stack; every other flag is ignored.
+ * Column c is a fixed expression of (entries in their order, column c of the weights, source, (out_h, out_w), interpolation, route): it
+ * does not depend on g, on the other columns or the column's place in the matrix, on host versus device output, on earlier calls or on
+ * whether a grid arrived as the shared grid or as n copies of it -- provided every sample is finite: an entry whose weights are exactly 0
+ * in all of a workgroup's columns is passed over without being sampled, where the loop below would add 0 x NaN for a non-finite sample.
+ * Bit identities: (1) column c holds the bits of the host loop acc = b; for i ascending: acc = acc + W[i, c] * double(S_i[h, w]);
+ * float32(acc), with S = vt_volume_warp_stack(..., weights = NULL) from the same handle with the same flags -- for every interpolation
+ * on both routes (a pixel that maps outside adds +0 to a sum that started at +0; with VT_ACCUMULATE the identity holds up to the sign of
+ * a zero found in out); (2) a one-hot column (W[k, c] = w, 0 elsewhere) holds vt_volume_warp_stack's image k under weight w.
+ * ONE workgroup per (chunk of 4 consecutive columns, 2-D output tile) (last_kernel 26, last_grid = column chunks x tiles chunk-major,
+ * last_tile = (1, TH, TW) of vt_volume_warp_stack) walks the n entries in ascending order with float64 accumulators in registers; per
+ * entry it runs vt_volume_warp_stack's steps with that call's tile, node block, per-tile route rule and patch allocation.  A tile
+ * classified wholly outside an entry adds nothing; with VT_ACCUMULATE a tile no entry reaches is not written.  The next entry's patch
+ * and the nodes of the entry after it are loaded while the current entry is sampled: with a grid per entry LDS holds NB = 3 node blocks,
+ * with a shared grid NB = 1 (loaded once per workgroup), then two patch allocations:
+ *     last_lds_bytes = 4 * NB * node_floats + 2 * allocation bytes
+ * node_floats = 2 x (largest node count over the tile rows) x (largest over the tile columns) rounded up to 4, the allocation
+ * vt_volume_warp_stack's; last_lds_dims = (2, Ly, Lx) of the allocation, (0, 0, 0) when no entry may stage.  No atomics, no memset.
+ * Tables and grids are uploaded per call, in one copy (n x (192 + 8 g) bytes + 8 bytes per node); no image but the g results exists.
+ * Bounds (VT_EUNSUPPORTED beyond, decided before any array is read): vt_volume_warp_stack's on grids and image, column chunks x tiles
+ * < 2^31, g x image bytes within size_t.  Checks in vt_volume_warp_stack's order; g <= 0, weights == NULL with g != 1, non-finite
+ * weights: VT_EINVAL.  Slab handles, filt_* without VT_STACK and VT_EDGE_SCIPY handles as for vt_volume_warp_stack.  Host `out`: returns
+ * after the copy back; VT_OUT_DEVICE: asynchronous on the handle's stream.  A refusal leaves the handle usable. */
+int vt_volume_warp_stack_sum(vt_volume_t* vol, int n, const float* m4x4s /* n x 16, or NULL = identity for every entry */,
+                             const float* grids /* n_grids x grid_h x grid_w x 2 */, int n_grids /* 1 = shared by all entries, or n */,
+                             int grid_h, int grid_w, const int32_t* planes /* n, or NULL */,
+                             int g, const double* weights /* n x g, C order, or NULL = all 1 (then g must be 1) */,
+                             int out_h, int out_w, float* out /* g images, C order */, int flags);
+int vt_volume_warp_stack_sum_f64(vt_volume_t* vol, int n, const double* m4x4s /* n x 16, or NULL = identity for every entry */,
+                                 const float* grids /* n_grids x grid_h x grid_w x 2 */, int n_grids /* 1 = shared by all entries, or n */,
+                                 int grid_h, int grid_w, const int32_t* planes /* n, or NULL */,
+                                 int g, const double* weights /* n x g, C order, or NULL = all 1 (then g must be 1) */,
+                                 int out_h, int out_w, float* out /* g images, C order */, int flags);
 
 /* ---- filter_stack: every image of a resident stack convolved with a 1-D filter along axis 1 or 2 -- the ramp filter of weighted
  * back-projection between alignment and reconstruction (after alignment the tilt axis lies along an array axis, and the filter runs along

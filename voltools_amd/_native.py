@@ -38,7 +38,7 @@ SYMBOLS = [
     'vt_volume_place', 'vt_volume_place_f64', 'vt_volume_backproject', 'vt_volume_backproject_f64',
     'vt_volume_backproject_boxes', 'vt_volume_backproject_boxes_f64',
     'vt_volume_warp', 'vt_volume_warp_f64', 'vt_volume_affine_stack', 'vt_volume_affine_stack_f64',
-    'vt_volume_warp_stack', 'vt_volume_warp_stack_f64', 'vt_volume_filter_stack',
+    'vt_volume_warp_stack', 'vt_volume_warp_stack_f64', 'vt_volume_warp_stack_sum', 'vt_volume_warp_stack_sum_f64', 'vt_volume_filter_stack',
     'vt_volume_correlate_stack', 'vt_volume_moments_stack',
 ]
 
@@ -141,6 +141,8 @@ def load():
     L.vt_volume_affine_stack_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]
     L.vt_volume_warp_stack.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]
     L.vt_volume_warp_stack_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_warp_stack_sum.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int]
+    L.vt_volume_warp_stack_sum_f64.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int]
     L.vt_volume_filter_stack.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int]
     L.vt_volume_correlate_stack.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]
     L.vt_volume_moments_stack.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]

@@ -280,6 +280,7 @@ int init_device(int dev)
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_backproject_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_backproject_boxes_kernels();
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_warp_kernels();
+            if (g_init_err[dev] == hipSuccess) g_init_err[dev] = init_warp_stack_sum_kernels();
             hipDeviceProp_t prop;
             if (g_init_err[dev] == hipSuccess) g_init_err[dev] = hipGetDeviceProperties(&prop, dev);
             if (g_init_err[dev] == hipSuccess) {
@@ -2562,6 +2563,28 @@ int do_warp(vt_volume* v, const double* m4x4, const float* grid, int gd, int gh,
     return res.finish();
 }
 
+// The grids of a warp_stack call (kinds 22, 26): checked, ranged (ranges: four floats per grid, warp_stack_grid_range's) and copied to dst
+// in ONE pass, in pieces that stay in the cache between the three.
+int warp_stack_take_grids(const float* grids, int n_grids, int gh, int gw, float* dst, float* ranges)
+{
+    constexpr size_t kPieceNodes = 32768;                   // 256 KiB
+    const size_t nodes = (size_t)gh * gw;
+    for (int k = 0; k < n_grids; ++k) {
+        float* const r = &ranges[4 * (size_t)k];
+        r[0] = r[2] = INFINITY; r[1] = r[3] = -INFINITY;
+        for (size_t at = 0; at < nodes; at += kPieceNodes) {
+            const size_t cnt = std::min(kPieceNodes, nodes - at), first = 2 * ((size_t)k * nodes + at);
+            if (!warp_stack_grid_range(grids + first, cnt, r)) {
+                size_t i = first;
+                while (std::isfinite(grids[i])) ++i;
+                return fail(VT_EINVAL, "grid node %zu component %d is not finite", i / 2, (int)(i % 2));
+            }
+            std::memcpy(dst + first, grids + first, 2 * cnt * sizeof(float));
+        }
+    }
+    return 0;
+}
+
 // n images of shape (oh, ow) from the handle's stack, image i from image planes[i] at rows 1 and 2 of matrix i (nullptr: the identity)
 // plus the float64 bilinear interpolation of grid i (n_grids == 1: of the one grid) of gh x gw x 2 float32, whose nodes span the output
 // image corner to corner (vt_kernels_warpstack.hip has the expression): one launch of kernel 22, n x tiles workgroups, do_affine_stack's
@@ -2608,24 +2631,7 @@ int do_warp_stack(vt_volume* v, int n, const MT* m4x4s, const float* grids, int 
     // the grids: checked, ranged and copied in ONE pass, in pieces that stay in the cache between the three -- with a dense field per
     // image this pass and the upload are the call
     std::vector<float> ranges((size_t)n_grids * 4);
-    {
-        constexpr size_t kPieceNodes = 32768;                   // 256 KiB
-        float* const dst = reinterpret_cast<float*>(v->h_batch_m.data() + grids_at);
-        const size_t nodes = (size_t)gh * gw;
-        for (int k = 0; k < n_grids; ++k) {
-            float* const r = &ranges[4 * (size_t)k];
-            r[0] = r[2] = INFINITY; r[1] = r[3] = -INFINITY;
-            for (size_t at = 0; at < nodes; at += kPieceNodes) {
-                const size_t cnt = std::min(kPieceNodes, nodes - at), first = 2 * ((size_t)k * nodes + at);
-                if (!warp_stack_grid_range(grids + first, cnt, r)) {
-                    size_t i = first;
-                    while (std::isfinite(grids[i])) ++i;
-                    return fail(VT_EINVAL, "grid node %zu component %d is not finite", i / 2, (int)(i % 2));
-                }
-                std::memcpy(dst + first, grids + first, 2 * cnt * sizeof(float));
-            }
-        }
-    }
+    if ((rc = warp_stack_take_grids(grids, n_grids, gh, gw, reinterpret_cast<float*>(v->h_batch_m.data() + grids_at), ranges.data()))) return rc;
     for (int i = 0; i < n; ++i) {
         double rows[8] = {0, 1, 0, 0, 0, 0, 1, 0};
         if (m4x4s) {
@@ -2648,6 +2654,84 @@ int do_warp_stack(vt_volume* v, int n, const MT* m4x4s, const float* grids, int 
     VT_HIP(launch_warp_stack(cfg, v->interp, v->d_src, res.ptr<float>(), v->d_zeros, device_entries(v), v->d_batch_m + kEntryDoubles * (size_t)n,
                              reinterpret_cast<const WarpStackHeader*>(v->d_batch_m + hdr_at),
                              reinterpret_cast<const float*>(v->d_batch_m + grids_at), n, p, lds_bytes, v->stream));
+    return res.finish();
+}
+
+// g images of shape (oh, ow): column c of the n x g weights (nullptr: one column of ones) over the n images do_warp_stack would write
+// unweighted, summed in float64 in ascending order and rounded once, the images never written (vt_kernels_warpstacksum.hip has the
+// expression): one launch of kernel 26, column chunks x tiles workgroups.  Checks in do_warp_stack's order; entries, grid pass, node block
+// and patch allocation are its own (warp_stack_fill_entry, warp_stack_take_grids, warp_stack_plan).  The tables travel in one upload:
+// n entries, the n x g weights (padded to an even count), the grid header, the grids.  MT: float or double matrices.  Does not read or
+// change the handle's own output shape.
+template <typename MT>
+int do_warp_stack_sum(vt_volume* v, int n, const MT* m4x4s, const float* grids, int n_grids, int gh, int gw, const int32_t* planes, int g,
+                      const double* weights, int oh, int ow, float* out, int flags)
+{
+    if (!v || !grids || !out) return fail(VT_EINVAL, "NULL argument");
+    int rc = check_batch_size(n);
+    if (rc || (rc = check_shape("output", 1, oh, ow)) || (rc = check_backproject_handle(v))) return rc;
+    if (g <= 0) return fail(VT_EINVAL, "column count %d", g);
+    if (!weights && g != 1) return fail(VT_EINVAL, "NULL weights with %d columns: without weights there is one column", g);
+    if (n_grids != 1 && n_grids != n) return fail(VT_EINVAL, "%d grids for %d entries: one shared grid, or one per entry", n_grids, n);
+    const int gd[2] = {gh, gw}, o[2] = {oh, ow};
+    for (int k = 0; k < 2; ++k)
+        if (gd[k] != 1 && (gd[k] < 2 || gd[k] > o[k]))
+            return fail(VT_EINVAL, "grid dims (%d,%d): per axis 1 node, or 2 up to the output's %d x %d", gh, gw, oh, ow);
+    // the bounds, before anything of the caller's arrays is read
+    const int64_t per_grid = (int64_t)gh * gw * 2;
+    if (per_grid > 0x7fffffffLL || per_grid * n_grids > 0x7fffffffLL)
+        return fail(VT_EUNSUPPORTED, "grids too large (%d grids of %d x %d nodes)", n_grids, gh, gw);
+    const int64_t grid_floats = per_grid * n_grids;
+    const bool cubic = is_cubic(v->interp);
+    const int cfg = stack_affine_pick_tile(cubic, oh, ow);
+    int T[3] = {1, 0, 0};
+    stack_affine_tile(cfg, &T[1], &T[2]);
+    const int nT[3] = {1, (oh + T[1] - 1) / T[1], (ow + T[2] - 1) / T[2]};
+    const int64_t tiles = (int64_t)nT[1] * nT[2];
+    const int64_t chunks = ((int64_t)g + kWarpStackSumChunk - 1) / kWarpStackSumChunk;
+    if (tiles * chunks > 0x7fffffffLL) return fail(VT_EUNSUPPORTED, "grid too large (%d columns x %lld tiles)", g, (long long)tiles);
+    const size_t image = (size_t)oh * ow;                      // < 2^31 by check_shape
+    if (image > (SIZE_MAX / sizeof(float)) / (size_t)g) return fail(VT_EUNSUPPORTED, "output too large (%d images)", g);
+    if ((size_t)g > (SIZE_MAX / sizeof(double) / 4) / (size_t)n) return fail(VT_EUNSUPPORTED, "weights too large (%d x %d)", n, g);
+    if ((rc = select_device(v)) || (m4x4s && (rc = check_finite_matrices(m4x4s, (size_t)n))) ||
+        (rc = check_finite_weights(weights, (size_t)n * (size_t)g)) || (rc = check_planes(v, n, planes, "")))
+        return rc;
+
+    const bool force_direct = (flags & VT_FORCE_DIRECT) && !(flags & VT_FORCE_TILED);
+    const bool accumulate = (flags & VT_ACCUMULATE) != 0;
+    constexpr size_t kHeaderDoubles = sizeof(WarpStackHeader) / sizeof(double);
+    const size_t n_w = (size_t)n * (size_t)g, n_wts = (n_w + 1) & ~(size_t)1;      // the header behind them stays 16-byte aligned
+    const size_t hdr_at = (size_t)n * kEntryDoubles + n_wts, grids_at = hdr_at + kHeaderDoubles;
+    if ((rc = begin_tables(v, grids_at + ((size_t)grid_floats + 1) / 2))) return rc;
+    ExtractEntry* const e = host_entries(v);
+    double* const w = v->h_batch_m.data() + kEntryDoubles * (size_t)n;
+    WarpStackHeader* const hd = reinterpret_cast<WarpStackHeader*>(v->h_batch_m.data() + hdr_at);
+    std::vector<float> ranges((size_t)n_grids * 4);
+    if ((rc = warp_stack_take_grids(grids, n_grids, gh, gw, reinterpret_cast<float*>(v->h_batch_m.data() + grids_at), ranges.data()))) return rc;
+    for (int i = 0; i < n; ++i) {
+        double rows[8] = {0, 1, 0, 0, 0, 0, 1, 0};
+        if (m4x4s) {
+            const MT* a = m4x4s + 16 * (size_t)i;
+            for (int k = 0; k < 8; ++k) rows[k] = (double)a[4 + k];
+        }
+        warp_stack_fill_entry(rows, planes ? planes[i] : i, cfg, cubic, oh, ow, force_direct, &e[i]);
+    }
+    if (weights) std::memcpy(w, weights, n_w * sizeof(double));
+    else std::fill(w, w + n_w, 1.0);
+    if (n_wts > n_w) w[n_w] = 0.0;
+    int L2[2], patch_bytes = 0;
+    warp_stack_plan(e, n, ranges.data(), n_grids, gd, cfg, cubic, oh, ow, hd, L2, &patch_bytes);
+    const int L[3] = {patch_bytes ? 2 : 0, L2[0], L2[1]};
+    const int lds_bytes = warp_stack_sum_lds_bytes(*hd, patch_bytes);
+    const AffineParams p = box_params(v, 1, oh, ow, nT);
+    record_launch(v, 26, T, L, lds_bytes, tiles * chunks);
+
+    ResultScope res(v, out, image * (size_t)g * sizeof(float), !(flags & VT_OUT_DEVICE));
+    if ((rc = res.open(accumulate)) || (rc = upload_tables(v))) return rc;
+    VT_HIP(launch_warp_stack_sum(cfg, v->interp, v->d_src, res.ptr<float>(), v->d_zeros, device_entries(v),
+                                 v->d_batch_m + kEntryDoubles * (size_t)n, reinterpret_cast<const WarpStackHeader*>(v->d_batch_m + hdr_at),
+                                 reinterpret_cast<const float*>(v->d_batch_m + grids_at), n, g, patch_bytes, accumulate, p, lds_bytes,
+                                 v->stream));
     return res.finish();
 }
 
@@ -3294,6 +3378,18 @@ int vt_volume_warp_f64(vt_volume_t* v, const double* m4x4, const float* grid, in
                        int out_w, float* out, int flags)
 {
     return do_warp(v, m4x4, grid, grid_d, grid_h, grid_w, out_d, out_h, out_w, out, flags);
+}
+
+int vt_volume_warp_stack_sum(vt_volume_t* v, int n, const float* m4x4s, const float* grids, int n_grids, int grid_h, int grid_w,
+                             const int32_t* planes, int g, const double* weights, int out_h, int out_w, float* out, int flags)
+{
+    return do_warp_stack_sum(v, n, m4x4s, grids, n_grids, grid_h, grid_w, planes, g, weights, out_h, out_w, out, flags);
+}
+
+int vt_volume_warp_stack_sum_f64(vt_volume_t* v, int n, const double* m4x4s, const float* grids, int n_grids, int grid_h, int grid_w,
+                                 const int32_t* planes, int g, const double* weights, int out_h, int out_w, float* out, int flags)
+{
+    return do_warp_stack_sum(v, n, m4x4s, grids, n_grids, grid_h, grid_w, planes, g, weights, out_h, out_w, out, flags);
 }
 
 int vt_volume_warp_stack(vt_volume_t* v, int n, const float* m4x4s, const float* grids, int n_grids, int grid_h, int grid_w,

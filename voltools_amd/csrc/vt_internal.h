@@ -423,6 +423,18 @@ hipError_t launch_warp_stack(int cfg, int interp, const float* src, float* out, 
                              const double* d_wts, const WarpStackHeader* d_hdr, const float* d_grids, int n, const AffineParams& p,
                              int lds_bytes, hipStream_t stream);
 
+// kind 22's images summed under g weight columns without being written (vt_kernels_warpstacksum.hip, kind 26): one workgroup per (chunk of
+// kWarpStackSumChunk consecutive columns, 2-D output tile) walks the n entries in ascending order with float64 accumulators in registers;
+// tile, entries, header, node block and patch allocation are kind 22's (warp_stack_fill_entry, warp_stack_plan).  d_wts: n x g, C order.
+// Dynamic LDS: one node block (shared grid) or three, then two patch allocations -- warp_stack_sum_lds_bytes.
+// accumulate: sums start from `out` as found, tiles no entry reaches are not written; otherwise every pixel is written.
+constexpr int kWarpStackSumChunk = 4;
+hipError_t init_warp_stack_sum_kernels();
+int warp_stack_sum_lds_bytes(const WarpStackHeader& hd, int patch_bytes);
+hipError_t launch_warp_stack_sum(int cfg, int interp, const float* src, float* out, const float* zeros16, const ExtractEntry* d_tab,
+                                 const double* d_wts, const WarpStackHeader* d_hdr, const float* d_grids, int n, int g, int patch_bytes,
+                                 bool accumulate, const AffineParams& p, int lds_bytes, hipStream_t stream);
+
 // a 1-D filter along axis 1 or 2 of every image of the stack (vt_kernels_filterstack.hip, kind 23): one workgroup per (entry, strip of
 // kFilterStrip lines across the unfiltered axis, segment of kFilterSeg outputs along the filtered axis), grid = n x strips x segments
 // entry-major.  The taps are walked kFilterChunk consecutive j at a time; per chunk the workgroup stages kFilterSeg + kFilterChunk - 1

@@ -60,52 +60,7 @@
 
 namespace vt {
 
-// The staged patch (Ly, Lx) of a tile of entry e whose nodes span [umin, umax] per source axis (index 0 is not read): stack_patch_dims'
-// formula on the affine extent pos - neg (with two terms per row the sum of their magnitudes, bit for bit) plus umax - umin.  False: the
-// extent is absurd or the patch exceeds kStackAffinePatchCap.  Float64 additions, floor and comparisons only: host and device agree.
-__host__ __device__ __forceinline__ bool warp_stack_patch(const ExtractEntry& e, const float (&umin)[3], const float (&umax)[3], int halo2,
-                                                          int (&L)[2])
-{
-#pragma unroll
-    for (int r = 1; r <= 2; ++r) {
-        const double spread = (double)umax[r] - (double)umin[r];
-        const double ext = (e.pos[r] - e.neg[r]) + spread;
-        if (!(ext < 4096.0)) return false;
-        L[r - 1] = (int)floor(ext + 2.0 * kBoxMargin) + 3 + halo2;
-    }
-    L[1] = (L[1] + 3 + 3) & ~3;                              // origin aligned down by up to 3, stride multiple of 4
-    return (int64_t)L[0] * L[1] * 4 <= (int64_t)kStackAffinePatchCap;
-}
-
-// the tile's geometry, wave-uniform
-struct WarpStackGeo {
-    int cl1, cl2;              // first cell of the node block per axis
-    int nn2;                   // nodes per row of the block
-    int su1, su2;              // node strides (floats) of the block; 0 on an axis with one node
-    int gm2_1, gm2_2;          // g_k - 2, at least 0
-    int o1, o2;                // origin of the staged patch
-    int Lx;                    // its row stride
-};
-
-// The lerps along axis 2 of the two node rows of cell row c1, per component: what the pixels of one column share while their cell row
-// stays the same.
-struct WarpStackRowLerp {
-    int c1;                    // the cell row the values belong to (-1: none yet)
-    double x0[2], x1[2];
-};
-
-__device__ __forceinline__ void warp_stack_row_lerp(const float* __restrict__ nodes, const WarpStackGeo& g, const int c1, const int c2,
-                                                    const double f2, WarpStackRowLerp& rl)
-{
-    const float* const q = nodes + 2 * (g.nn2 * (c1 - g.cl1) + (c2 - g.cl2));
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const double a00 = (double)q[c], a01 = (double)q[g.su2 + c], a10 = (double)q[g.su1 + c], a11 = (double)q[g.su1 + g.su2 + c];
-        rl.x0[c] = fma(f2, a01 - a00, a00);
-        rl.x1[c] = fma(f2, a11 - a10, a10);
-    }
-    rl.c1 = c1;
-}
+// warp_stack_patch, WarpStackGeo and the row lerp live in vt_warp_common.h: kind 26 (vt_kernels_warpstacksum.hip) runs the same text.
 
 // One pixel (h, w) of the output: the chain, the displacement from the node block in LDS, the inside test (WHOLE: none), the sample.
 // A thread's pixels lie in one column, so the lerps along axis 2 are formed again only when the cell row changes (rl) -- the same

@@ -1252,19 +1252,9 @@ class StaticVolume:
         ms = stack_matrices(shifts, rotations, scales, self.shape[1:], output_shape, rotation_units)
         return self.affine_stack(ms, output_shape, weights, profile, output, planes=planes)
 
-    def warp_stack(self, displacements, matrices=None, output_shape=None, weights=None, profile: bool = False, output=None, *,
-                   planes=None, _flags: int = 0) -> Union[np.ndarray, None]:
-        """``affine_stack`` with a 2-D displacement field per image: ``out[i, h, w] = float32(weights[i] * B_i[h, w])`` with ``B_i[h, w]``
-        image ``planes[i]`` interpolated in two dimensions at ``(y, x) = M_i . (h, w, 1) + u_i(h, w)``, 0 outside the image.
-        ``displacements``: control grids ``(n, gH, gW, 2)``, or ``(gH, gW, 2)`` for one grid shared by every entry, taken as float32;
-        component 0 moves ``y``, component 1 moves ``x``, in source pixels.  The nodes span the output image corner to corner
-        (``utils.stack_grid_nodes``), ``u_i`` is their bilinear interpolation in float64 -- ``warp``'s grid rule on axes 1 and 2.  Per axis
-        either one node or 2 up to the output size; a grid of the output's shape is a dense field.  ``matrices``: None for the identity,
-        or ``(n, 3, 3)`` / ``(n, 4, 4)`` as ``affine_stack`` takes them; float64 keeps its precision.  ``n`` is the number of matrices if
-        given, else the number of grids, else ``T``.  ``output_shape``, ``planes``, ``weights`` and ``output`` are ``affine_stack``'s.
-        Returns a float32 array ``(n, Ho, Wo)``, or fills ``output`` and returns None on a GPU device.  An image does not depend on the
-        rest of the batch.  ``device='cpu'`` evaluates the same float64 coordinates in numpy and hands them to
-        ``scipy.ndimage.map_coordinates`` per entry."""
+    def _warp_stack_arguments(self, displacements, matrices, output_shape, planes, take_weights):
+        """What ``warp_stack`` and ``warp_stack_sum`` share: the checked arguments ``(disp, shared, ms, n, shape, gshape, w, pl)``.
+        ``take_weights(n)`` checks and returns the call's weights; it runs where ``warp_stack`` has always checked them."""
         disp = np.asarray(displacements)
         if disp.ndim not in (3, 4) or disp.shape[-1] != 2 or 0 in disp.shape:
             raise ValueError('displacements must have shape (n, gH, gW, 2) or (gH, gW, 2)')
@@ -1299,11 +1289,7 @@ class StaticVolume:
             raise ValueError(f'displacements of grid shape {gshape}: per axis 1 node, or 2 up to the output size {shape[1:]}')
         if not np.isfinite(disp).all():
             raise ValueError('displacements must be finite')
-        w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
-        if w.shape != (n,):
-            raise ValueError(f'weights must have shape ({n},)')
-        if not np.isfinite(w).all():
-            raise ValueError('weights must be finite')
+        w = take_weights(n)
         if planes is None:
             if n != self.shape[0]:
                 raise ValueError(f'{n} entries for a stack of {self.shape[0]} images: planes must be given')
@@ -1315,23 +1301,51 @@ class StaticVolume:
             if pl.min() < 0 or pl.max() >= self.shape[0]:
                 raise ValueError(f'planes must lie inside [0, {self.shape[0]})')
             pl = np.ascontiguousarray(pl, dtype=np.int32)
+        return disp, shared, ms, n, shape, gshape, w, pl
+
+    def _warp_stack_cpu_samples(self, disp, shared, ms, n, shape, pl):
+        """The ``device='cpu'`` samples of ``warp_stack`` and ``warp_stack_sum``: entry by entry the float32 image ``B_i``, unweighted."""
+        order, prefilter = _scipy_arguments(self.interpolation)
+        coeffs = {}
+        for i in range(n):
+            k = i if pl is None else int(pl[i])
+            if k not in coeffs:     # spline_filter per plane: the planes are independent images
+                img = np.asarray(self.data[k], dtype=np.float64)
+                coeffs[k] = spline_filter(img, order, output=np.float64, mode='constant') if prefilter else img
+            yy, xx = _warp_stack_coordinates(disp if shared else disp[i], np.eye(4) if ms is None else ms[i].astype(np.float64), shape[1:])
+            one = map_coordinates(coeffs[k], [yy, xx], order=order, mode='constant', cval=0.0, prefilter=False, output=np.float64)
+            yield one.astype(np.float32)
+
+    def warp_stack(self, displacements, matrices=None, output_shape=None, weights=None, profile: bool = False, output=None, *,
+                   planes=None, _flags: int = 0) -> Union[np.ndarray, None]:
+        """``affine_stack`` with a 2-D displacement field per image: ``out[i, h, w] = float32(weights[i] * B_i[h, w])`` with ``B_i[h, w]``
+        image ``planes[i]`` interpolated in two dimensions at ``(y, x) = M_i . (h, w, 1) + u_i(h, w)``, 0 outside the image.
+        ``displacements``: control grids ``(n, gH, gW, 2)``, or ``(gH, gW, 2)`` for one grid shared by every entry, taken as float32;
+        component 0 moves ``y``, component 1 moves ``x``, in source pixels.  The nodes span the output image corner to corner
+        (``utils.stack_grid_nodes``), ``u_i`` is their bilinear interpolation in float64 -- ``warp``'s grid rule on axes 1 and 2.  Per axis
+        either one node or 2 up to the output size; a grid of the output's shape is a dense field.  ``matrices``: None for the identity,
+        or ``(n, 3, 3)`` / ``(n, 4, 4)`` as ``affine_stack`` takes them; float64 keeps its precision.  ``n`` is the number of matrices if
+        given, else the number of grids, else ``T``.  ``output_shape``, ``planes``, ``weights`` and ``output`` are ``affine_stack``'s.
+        Returns a float32 array ``(n, Ho, Wo)``, or fills ``output`` and returns None on a GPU device.  An image does not depend on the
+        rest of the batch.  ``device='cpu'`` evaluates the same float64 coordinates in numpy and hands them to
+        ``scipy.ndimage.map_coordinates`` per entry."""
+        def take_weights(n):
+            w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (n,):
+                raise ValueError(f'weights must have shape ({n},)')
+            if not np.isfinite(w).all():
+                raise ValueError('weights must be finite')
+            return w
+        disp, shared, ms, n, shape, gshape, w, pl = self._warp_stack_arguments(displacements, matrices, output_shape, planes, take_weights)
         if output is not None and tuple(getattr(output, 'shape', ())) != shape:
             raise ValueError(f'output must have shape {shape}')
         if self.interpolation.startswith('filt_') and not self.stack:
             raise ValueError('warp_stack with a filt_* interpolation needs in-plane coefficients: build the volume with stack=True')
         if self.device == 'cpu':
-            order, prefilter = _scipy_arguments(self.interpolation)
             res = np.empty(shape, dtype=np.float32)
-            coeffs = {}
             t_start = time.time()
-            for i in range(n):
-                k = i if pl is None else int(pl[i])
-                if k not in coeffs:     # spline_filter per plane: the planes are independent images
-                    img = np.asarray(self.data[k], dtype=np.float64)
-                    coeffs[k] = spline_filter(img, order, output=np.float64, mode='constant') if prefilter else img
-                yy, xx = _warp_stack_coordinates(disp if shared else disp[i], np.eye(4) if ms is None else ms[i].astype(np.float64), shape[1:])
-                one = map_coordinates(coeffs[k], [yy, xx], order=order, mode='constant', cval=0.0, prefilter=False, output=np.float64)
-                res[i] = (0.0 + w[i] * one.astype(np.float32).astype(np.float64)).astype(np.float32)
+            for i, one in enumerate(self._warp_stack_cpu_samples(disp, shared, ms, n, shape, pl)):
+                res[i] = (0.0 + w[i] * one.astype(np.float64)).astype(np.float32)
             if profile:
                 print(f'{n} images warped in {(time.time() - t_start) * 1000:.3f}ms')
             if output is None:
@@ -1357,6 +1371,94 @@ class StaticVolume:
         if profile:
             print(f'{n} images warped in {self.timer_stop():.3f}ms')
         return result
+
+    def warp_stack_sum(self, displacements, matrices=None, output_shape=None, weights=None, profile: bool = False, output=None, *,
+                       planes=None, accumulate: bool = False, _flags: int = 0) -> Union[np.ndarray, None]:
+        """The images ``warp_stack`` would write, summed without being written: ``out[c] = float32(b + sum_i W[i, c] * B_i)`` with ``B_i``
+        ``warp_stack``'s unweighted float32 image ``i``, summed in float64 in ascending ``i`` (each product rounded, then each sum) and
+        rounded once -- the motion-corrected sum of a movie.  ``displacements``, ``matrices``, ``output_shape`` and ``planes`` are
+        ``warp_stack``'s.  ``weights``: None (ones) or ``(n,)`` for one sum, returned as ``(Ho, Wo)``; or ``(n, G)`` for ``G`` sums from
+        one sampling of every image (all frames, even and odd frames, exposure windows), returned as ``(G, Ho, Wo)``; float64.
+        ``accumulate=True`` starts the sums from ``output`` as found (``b``), which must then be given; else ``b = 0``.  A sum does
+        not depend on ``G``, on the other columns or on its place among them.  Returns a float32 array, or fills ``output`` of that
+        shape and returns None on a GPU device.  ``device='cpu'`` sums the samples of its own ``warp_stack(weights=None)`` by the same
+        expression."""
+        holder = {}
+
+        def take_weights(n):
+            w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+            if w.ndim not in (1, 2) or w.shape[0] != n or 0 in w.shape:
+                raise ValueError(f'weights must have shape ({n},) or ({n}, G)')
+            if not np.isfinite(w).all():
+                raise ValueError('weights must be finite')
+            holder['single'] = w.ndim == 1
+            return w.reshape(n, -1)
+        disp, shared, ms, n, shape, gshape, w, pl = self._warp_stack_arguments(displacements, matrices, output_shape, planes, take_weights)
+        g = w.shape[1]
+        full = (g, shape[1], shape[2])
+        oshape = full[1:] if holder['single'] else full
+        if accumulate and output is None:
+            raise ValueError('accumulate=True adds into output, which must be given')
+        if output is not None and tuple(getattr(output, 'shape', ())) != oshape:
+            raise ValueError(f'output must have shape {oshape}')
+        if self.interpolation.startswith('filt_') and not self.stack:
+            raise ValueError('warp_stack_sum with a filt_* interpolation needs in-plane coefficients: build the volume with stack=True')
+        if self.device == 'cpu':
+            t_start = time.time()
+            acc = np.asarray(output, dtype=np.float32).astype(np.float64).reshape(full) if accumulate else np.zeros(full, dtype=np.float64)
+            for i, one in enumerate(self._warp_stack_cpu_samples(disp, shared, ms, n, shape, pl)):
+                s64 = one.astype(np.float64)
+                for c in range(g):
+                    acc[c] = acc[c] + w[i, c] * s64
+            res = acc.astype(np.float32).reshape(oshape)
+            if profile:
+                print(f'{n} images warped and summed in {(time.time() - t_start) * 1000:.3f}ms')
+            if output is None:
+                return res
+            output[...] = res
+            return output
+        flags = _flags | (_native.ACCUMULATE if accumulate else 0)
+        if output is None:
+            result = _native.host_result(oshape, self._dev)
+            ptr, is_dev = result.ctypes.data, False
+        else:
+            ptr, is_dev, _ = _native.resolve_output(output, oshape, self._dev)
+            result = None
+        if is_dev:
+            flags |= _native.OUT_DEVICE
+        if profile:
+            self.timer_start()
+        pl_ptr = None if pl is None else pl.ctypes.data
+        m_ptr = None if ms is None else ms.ctypes.data
+        fn = self._lib.vt_volume_warp_stack_sum_f64 if ms is not None and ms.dtype == np.float64 else self._lib.vt_volume_warp_stack_sum
+        _native.check(fn(self._handle, n, m_ptr, disp.ctypes.data, 1 if shared else n, gshape[0], gshape[1], pl_ptr, g, w.ctypes.data,
+                         shape[1], shape[2], ptr, flags), 'vt_volume_warp_stack_sum')
+        if profile:
+            print(f'{n} images warped and summed in {self.timer_stop():.3f}ms')
+        return result
+
+    def motion_corrected_sum(self, displacements=None, shifts=None, halves: bool = False, **kw) -> Union[np.ndarray, None]:
+        """The sum of this stack's frames after motion correction, one ``warp_stack_sum`` call.  ``displacements``: the per-patch
+        displacement grids as ``find_shifts(..., patch_grid=...)`` returns them, ``(n, gH, gW, 2)`` or one shared ``(gH, gW, 2)``;
+        None = no local motion (one zero node).  ``shifts``: ``(n, 2)`` whole-frame shifts ``(y, x)``, turned into translation matrices
+        by ``utils.stack_matrices`` as ``align_stack`` does; None = none.  ``halves=True`` returns ``(3, Ho, Wo)``: the sum of all
+        frames, of the even ones and of the odd ones, from one sampling.  Further keywords go to ``warp_stack_sum`` (``output_shape``,
+        ``planes``, ``output``, ``accumulate``, ``profile``)."""
+        if 'weights' in kw or 'matrices' in kw:
+            raise ValueError('motion_corrected_sum chooses weights and matrices itself: use warp_stack_sum')
+        if displacements is None:
+            displacements = np.zeros((1, 1, 2), dtype=np.float32)
+        ms = None
+        if shifts is not None:
+            ms = stack_matrices(shifts, None, None, self.shape[1:], kw.get('output_shape'))
+        disp = np.asarray(displacements)
+        n = ms.shape[0] if ms is not None else (disp.shape[0] if disp.ndim == 4 else self.shape[0])
+        weights = None
+        if halves:
+            weights = np.ones((n, 3), dtype=np.float64)
+            weights[1::2, 1] = 0.0
+            weights[0::2, 2] = 0.0
+        return self.warp_stack_sum(displacements, ms, weights=weights, **kw)
 
     # -- a 1-D filter per image of the stack (extension: the ramp filter of weighted back-projection, low-pass, derivative taps) ----
     def filter_stack(self, taps, axis: int = 2, weights=None, pad: str = 'zero', profile: bool = False, output=None, *,
